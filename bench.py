@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- HSTU attention fwd+bwd throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload M-full|M-jag|M-targets|C2|C3|C3-bias|C4|C5]
+    python bench.py --gpus N --steps K --warmup W [--workload M-full|M-jag|M-targets|C2|C3|C3-bias|C4|C5] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and nothing else: inputs, pre-warm, W warm-up steps, K timed steps, the outputs of
+the last timed step under DIR (``--dump-outputs``), one JSON line (``value``, ``ms_per_step``, the roofline of the timed
+steps).  ``--full`` adds everything else the line used to carry: the oracle check of the timed batch, telemetry, the other
+workloads, calibration, the RCCL probe (a one-rank communicator at --gpus 1), the STU-layer section and the CPU baselines.
 
 A *step* is one pass of the hot path -- hstu attention forward + backward through the C ABI (libhstu_hip.so) -- over one
 batch of synthetic jagged user sequences that is already resident in HBM.  Default workload = the metric shape M
@@ -21,7 +26,7 @@ all-reduce that step performs.
 
 Every section runs ~0.3 s of its own steps UNTIMED in front of its W warm-up steps (``--prewarm-s``: the clock / power ramp after an
 idle gap otherwise lands in the first counted steps), then W warm-up steps, then exactly K timed steps between barrier +
-synchronize.  Rank 0 prints ONE JSON line (contract in the task statement) with the extra objects
+synchronize.  Rank 0 prints ONE JSON line (contract in the task statement) with the extra objects (all but roofline: --full)
   roofline      -- dominant kernel (backward): algorithmic bytes / HIP-event kernel time vs 8 TB/s; kernel names come from
                    the library (hstu_attn_*_kernel_name); ``traffic`` = HBM bytes from committed PMC passes of the SAME
                    workload / dtype / head dim / users (``traffic_source`` says which), null otherwise
@@ -84,8 +89,39 @@ def _event_ms(pairs):
     return statistics.mean(a.elapsed_time(b) for a, b in pairs)
 
 
-def attention_section(args, rank, world, device, telem=None):
-    """the timed region of the headline number: K steps of attention fwd (+ bwd), bracketed by barrier + synchronize"""
+DUMP_BYTES = 60_000_000      # all files of --dump-outputs together (headers aside: they add ~128 bytes each)
+
+
+def sample_outputs(named, seed=0):
+    """name -> float32 host copy of each tensor.  The budget is split evenly; a tensor with more rows (dim 0) than its share
+    holds keeps a fixed subset of them, drawn with ``seed`` and sorted -- the same rows for every tensor of that row count,
+    and for every run with the same arguments (the inputs are seeded too), so two builds compare output for output."""
+    res, rows_of = {}, {}
+    share = DUMP_BYTES // len(named)
+    for name, t in named.items():
+        t = t.detach()
+        n = t.shape[0]
+        keep = min(n, share // (4 * (t.numel() // n)))
+        if keep < n:
+            if (n, keep) not in rows_of:
+                idx = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+                rows_of[(n, keep)] = idx.to(t.device)
+            t = t.index_select(0, rows_of[(n, keep)])
+        res[name] = t.float().cpu().numpy()
+    return res
+
+
+def write_outputs(outputs, out_dir):
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def attention_section(args, rank, world, device, telem=None, outputs=None):
+    """the timed region of the headline number: K steps of attention fwd (+ bwd), bracketed by barrier + synchronize.
+    ``outputs`` (a dict): filled with host copies of what the last timed step returned (sample_outputs)"""
     from generative_recommenders_amd import data_parallel as dp
     from generative_recommenders_amd.ops import _launch
 
@@ -101,6 +137,7 @@ def attention_section(args, rank, world, device, telem=None):
     alpha = d**-0.5
     fwd_only = wl == "C5"
     kernels = {}
+    grad_names = ("dq", "dk", "dv")      # what bwd() returns, in order
 
     if wl == "C5":
         delta, layers = 256, 24
@@ -137,6 +174,8 @@ def attention_section(args, rank, world, device, telem=None):
 
         def bwd():
             return torch.autograd.grad(state["out"], (q, k, v, bias._pos_w, bias._ts_w), g)
+
+        grad_names = ("dq", "dk", "dv", "d_pos_w", "d_ts_w")
 
         fwd_bytes = L * H * 4 * d * es + B * N * 8
         bwd_bytes = L * H * 7 * d * es + B * N * 8
@@ -180,12 +219,15 @@ def attention_section(args, rank, world, device, telem=None):
     # the sections -- runs a CPU checker, and drops to its lowest power state; the first tens of milliseconds of load then include
     # the clock / power ramp, seen as ONE step of 40-50 ms among steps of 1-3 ms (profiles/r05_bench_b_default_forward_outlier.json,
     # M-jag in r05_bench_c_default.json).  Keep the kernels of this section running for ~0.3 s before anything is counted.
+    # (every loop holds bwd()'s result until the next step returns its own, as the timed loop must for the last one: the allocator
+    # then holds the same blocks in all three, and the timed steps allocate nothing the warm-up did not)
+    grads = None
     prewarm_steps = 0
     t_pre = time.perf_counter()
     while time.perf_counter() - t_pre < getattr(args, "prewarm_s", 0.3) and prewarm_steps < 400:
         fwd()
         if bwd is not None:
-            bwd()
+            grads = bwd()
         prewarm_steps += 1
         if prewarm_steps % 8 == 0:
             torch.cuda.synchronize()
@@ -195,7 +237,7 @@ def attention_section(args, rank, world, device, telem=None):
     for _ in range(args.warmup):
         fwd()
         if bwd is not None:
-            bwd()
+            grads = bwd()
     if telem is not None:
         torch.cuda.synchronize()
         telem.stop()
@@ -210,12 +252,14 @@ def attention_section(args, rank, world, device, telem=None):
         out = fwd()
         ev[i][1].record()
         if bwd is not None:
-            bwd()
+            grads = bwd()
         ev[i][2].record()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     t1 = time.perf_counter()
+    if outputs is not None:
+        outputs.update(sample_outputs(dict(out=out, **dict(zip(grad_names, grads or ())))))
     elapsed = dp.max_over_ranks(t1 - t0, device)
     fwd_ms = _event_ms([(e[0], e[1]) for e in ev])
     bwd_ms = _event_ms([(e[1], e[2]) for e in ev]) if bwd is not None else 0.0
@@ -1009,7 +1053,7 @@ def _run(args, out):
     # The CPU baselines (10 + 8 s of host work on rank 0) run BEFORE the process group exists: the other ranks wait in the
     # rendezvous of init_process_group (a store wait), not inside a collective under the RCCL watchdog.
     cpu_res = None
-    if int(os.environ.get("RANK", "0")) == 0 and not args.no_cpu:
+    if args.full and int(os.environ.get("RANK", "0")) == 0 and not args.no_cpu:
         try:
             cpu_res = cpu_baseline(args)
         except Exception as e:  # pragma: no cover
@@ -1017,7 +1061,7 @@ def _run(args, out):
         torch.set_num_threads(max(1, min(8, len(os.sched_getaffinity(0)))))
     # (--gpus 1: a ONE-rank RCCL communicator -- the library, its version string and the reducer's stream discipline on the one GPU
     # there is: the layer section's gradient buckets then really go through ncclAllReduce; HSTU_BENCH_SINGLE_RANK_RCCL=0 turns it off)
-    single = int(os.environ.get("WORLD_SIZE", "1")) == 1 and os.environ.get("HSTU_BENCH_SINGLE_RANK_RCCL", "1") != "0"
+    single = args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and os.environ.get("HSTU_BENCH_SINGLE_RANK_RCCL", "1") != "0"
     if single:
         os.environ.setdefault("MASTER_PORT", str(_free_port()))
     try:
@@ -1036,8 +1080,11 @@ def _run(args, out):
     device = torch.device("cuda", dev_index)
     _lib.lib()
 
-    telem = Telemetry(device) if rank == 0 else None
-    att = attention_section(args, rank, world, device, telem)
+    telem = Telemetry(device) if rank == 0 and args.full else None
+    outputs = {} if rank == 0 and args.dump_outputs else None
+    att = attention_section(args, rank, world, device, telem, outputs)
+    if outputs is not None:
+        write_outputs(outputs, args.dump_outputs)
     value = world * att["users"] * args.steps / att["elapsed"]
     N, H, d = args.max_seq_len, args.heads, args.head_dim
     what = "fwd" if att["fwd_only"] else "fwd+bwd"
@@ -1063,6 +1110,20 @@ def _run(args, out):
         "prewarm_steps": att["prewarm_steps"], "prewarm_s": getattr(args, "prewarm_s", 0.3),
     }
     res["roofline"], res["roofline_fwd"], res["roofline_fwd_bwd"] = rooflines(att, args.workload)
+    attach_traffic(res, args, att)
+    if args.full:
+        _full_sections(res, args, rank, world, device, att, telem, cpu_res)
+    if rank == 0:
+        out.emit(json.dumps(res))
+    if dist.is_initialized():
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def _full_sections(res, args, rank, world, device, att, telem, cpu_res):
+    """what --full adds to the line behind the headline"""
+    from generative_recommenders_amd import data_parallel as dp
+
     res["parity_at_this_size"] = att["parity"] if att.get("parity") else (
         "by invariance only: batch-composition bit-exactness, delta == tail of full, linearity in V "
         "(tests/test_attention_gpu.py); the reference-minted vectors at this head shape are "
@@ -1070,7 +1131,6 @@ def _run(args, out):
     if telem is not None:
         res["telemetry"] = {"headline": telem.summary(),
                             "when": "sampled during the warm-up steps in front of each timed loop and an untimed replay of the same steps behind it, never inside a timed region"}
-    attach_traffic(res, args, att)
     if args.workload == "M-full" and not args.no_extra:
         res["extra_workloads"] = extra_workloads(args, rank, world, device)
     if rank == 0:
@@ -1102,11 +1162,6 @@ def _run(args, out):
             res["layer"] = {"error": repr(e)[:300]}
     if rank == 0 and cpu_res is not None:
         res["cpu_baseline"] = cpu_res
-    if rank == 0:
-        out.emit(json.dumps(res))
-    if dist.is_initialized():
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 def _free_port():
@@ -1137,18 +1192,26 @@ def main():
     ap.add_argument("--layer-dropout", type=float, default=0.1, help="output_dropout_ratio of the layer section (DLRM-v3: 0.1)")
     ap.add_argument("--no-extra", action="store_true", help="skip the short runs of the other workloads (extra_workloads)")
     ap.add_argument("--layer-tunableop", action="store_true",
-                    help="let PyTorch's TunableOp pick the hipBLASLt / rocBLAS solution of the layer section's six GEMM shapes during its "
+                    help="--full: let PyTorch's TunableOp pick the hipBLASLt / rocBLAS solution of the layer section's six GEMM shapes during its "
                          "warm-up (~20 s; measured 15.1 -> 14.5 ms per step, profiles/r03_layer_tunableop.txt); off by default")
     ap.add_argument("--extra-steps", type=int, default=8)
     ap.add_argument("--prewarm-s", type=float, default=0.3, help="seconds of untimed steps in front of every section's warm-up steps (clock / power ramp)")
-    ap.add_argument("--parity-users", type=int, default=32, help="users of the timed batch checked against the oracle after the timed loop (0: off)")
+    ap.add_argument("--parity-users", type=int, default=32, help="--full: users of the timed batch checked against the oracle after the timed loop (0: off)")
     ap.add_argument("--cpu-users", type=int, default=128)
     ap.add_argument("--cpu-threads", type=int, default=32)
     ap.add_argument("--sort-by-length", type=int, default=None, help="1: heavy-first workgroup order (default: on for C3)")
     ap.add_argument("--no-layer", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--selftest-dist", action="store_true", help="CPU / gloo run of the N-rank scaffolding only (tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: oracle check of the timed batch, telemetry, the other workloads, calibration, "
+                         "RCCL probe, STU-layer section, CPU baselines (--no-extra / --no-layer / --no-cpu / --parity-users 0 drop parts)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (out and the gradients) as DIR/<name>.npy, float32; a fixed seeded "
+                         "sample of rows where the whole would exceed 60 MB")
     args = ap.parse_args()
+    if not args.full:
+        args.parity_users = 0
     n, h, d, users, _ = WORKLOADS[args.workload]
     args.max_seq_len = args.max_seq_len or n
     args.heads = args.heads or h

@@ -1,6 +1,6 @@
 """CPU tests of bench.py's host-side helpers (no kernels): the telemetry sampler without hwmon nodes, the oracle check of a
 sample of the timed batch (fed with the oracle's own results, so the arithmetic of the check is what is tested), the committed
-PMC traffic file the line attaches, and the workload table."""
+PMC traffic file the line attaches, the workload table and the row sample of --dump-outputs."""
 
 import importlib.util
 import json
@@ -114,3 +114,21 @@ def test_workload_table_and_lengths():
         ln = bench.make_lengths(wl if wl not in ("M-targets", "C4", "C5", "L2048") else "M-jag", 64, n, gen, "cpu")
         assert ln.shape == (64,) and int(ln.max()) <= n and int(ln.min()) >= 0
     assert float(np.mean(bench.make_lengths("M-full", 8, 200, gen, "cpu").numpy())) == 200.0
+
+
+def test_sampled_outputs_stay_in_budget_and_draw_the_same_rows_every_time():
+    """--dump-outputs: float32 copies; tensors too large for their share of the budget keep one seeded, sorted set of rows (the
+    same for every tensor of that row count and every call), small ones go out whole"""
+    bench = _bench()
+    rows = 40000
+    big = torch.arange(rows, dtype=torch.float32)[:, None, None].expand(rows, 4, 128)       # row i holds i
+    small = torch.randn(423).bfloat16()
+    named = dict(out=big, dq=big * 2, dk=big, dv=big, d_pos_w=small)
+    a, b = bench.sample_outputs(named), bench.sample_outputs(named)
+    assert sum(x.nbytes for x in a.values()) <= bench.DUMP_BYTES
+    assert all(x.dtype == np.float32 for x in a.values()) and set(a) == set(named)
+    kept = a["out"][:, 0, 0]
+    assert 0 < len(kept) < rows and np.all(np.diff(kept) > 0)          # a sorted subset of distinct rows...
+    assert np.array_equal(a["dq"][:, 0, 0], 2 * kept)                   # ...the same rows in every tensor
+    assert all(np.array_equal(a[k], b[k]) for k in a)                   # ...and in every call
+    assert np.array_equal(a["d_pos_w"], small.float().numpy())

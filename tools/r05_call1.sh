@@ -15,10 +15,10 @@ import torch
 from generative_recommenders_amd.ops import _launch
 print(_launch.attn_bwd_kernel_name(torch.bfloat16, 128, 128, 200))"
 echo "== A/B: fold"
-HSTU_BWD_W16=0 timeout 300 python bench.py --no-layer --no-cpu --no-extra --steps 30 --warmup 10 2>&1 | tail -1 | python -c "
+HSTU_BWD_W16=0 timeout 300 python bench.py --full --no-layer --no-cpu --no-extra --steps 30 --warmup 10 2>&1 | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('fold', d['roofline']['kernel'], 'fwd', d['roofline_fwd']['avg_launch_ms'], 'bwd', d['roofline']['avg_launch_ms'], d['roofline']['frac'], 'parity', d['parity_at_this_size'])"
 echo "== A/B: w16"
-HSTU_BWD_W16=1 timeout 300 python bench.py --no-layer --no-cpu --no-extra --steps 30 --warmup 10 2>&1 | tail -1 | python -c "
+HSTU_BWD_W16=1 timeout 300 python bench.py --full --no-layer --no-cpu --no-extra --steps 30 --warmup 10 2>&1 | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('w16', d['roofline']['kernel'], 'fwd', d['roofline_fwd']['avg_launch_ms'], 'bwd', d['roofline']['avg_launch_ms'], d['roofline']['frac'], 'parity', d['parity_at_this_size'])"
 for v in 96 64 32; do
   if [ -f tests/probe/libhstu_w16a${v}.so ]; then
@@ -28,7 +28,7 @@ import json,sys; d=json.loads(sys.stdin.read()); print('w16 ablate', d['roofline
   fi
 done
 echo "== bench default"
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -3 $OUT/bench_default.err
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -3 $OUT/bench_default.err
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r05_call1/bench_default.json').read().strip().splitlines()[-1])
@@ -41,7 +41,7 @@ for k,v in (L.get('projections') or {}).items(): print('   ', k, v)
 for k,v in d['extra_workloads'].items(): print(' ', k, {x: v.get(x) for x in ('fwd_ms','bwd_ms','frac_fwd','frac_bwd','frac_fwd_bwd','error')})
 PY
 echo "== layer: dbeta stream A/B"
-for m in 1 0; do HSTU_DBETA_STREAM=$m timeout 300 python bench.py --no-cpu --no-extra --steps 5 --warmup 2 --parity-users 0 2>&1 | tail -1 | python -c "
+for m in 1 0; do HSTU_DBETA_STREAM=$m timeout 300 python bench.py --full --no-cpu --no-extra --steps 5 --warmup 2 --parity-users 0 2>&1 | tail -1 | python -c "
 import json,sys,os; d=json.loads(sys.stdin.read()); L=d['layer']; print('dbeta_stream', os.environ.get('HSTU_DBETA_STREAM'), L.get('ms_per_step'), L.get('error'))"; done
 } > $OUT/log.txt 2>&1
 tail -150 $OUT/log.txt | cut -c1-600

@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_compute_gpu.py tests/test_swish_layer_no
 for rep in 1 2; do
 for lib in "" $PWD/tests/probe/libhstu_slowsig.so; do
 echo "== lib=${lib:-default}"
-HSTU_HIP_LIBRARY=$lib timeout 300 python bench.py --no-cpu --no-extra --steps 20 --warmup 5 2>/dev/null | tail -1 | python -c "
+HSTU_HIP_LIBRARY=$lib timeout 300 python bench.py --full --no-cpu --no-extra --steps 20 --warmup 5 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); L=d['layer']
 print('layer ms', round(L['ms_per_step'],3), 'two-node', round(L['two_node_layers']['ms_per_step'],3), 'dropout_off', round(L['dropout_off']['ms_per_step'],3), 'no_recompute', round(L['no_recompute']['ms_per_step'],3))"
 done; done
