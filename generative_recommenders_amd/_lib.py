@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("HSTU_HIP_LIBRARY") or os.path.join(_HERE, "libhstu_hi
 ABI_VERSION = 13
 
 HSTU_DTYPE_BF16, HSTU_DTYPE_F16, HSTU_DTYPE_F32 = 0, 1, 2
+HSTU_DTYPE_FP8_E4M3 = 3     # attention forward only: e4m3 q / k / v, bf16 out
 HSTU_INDEX_I32, HSTU_INDEX_I64 = 0, 1
 
 
@@ -61,6 +62,15 @@ class HstuAttnBwdParams(C.Structure):
     ]
 
 
+class HstuFp8Descale(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p),
+        ("q_batch_stride", C.c_int64), ("q_head_stride", C.c_int64),
+        ("k_batch_stride", C.c_int64), ("k_head_stride", C.c_int64),
+        ("v_batch_stride", C.c_int64), ("v_head_stride", C.c_int64),
+    ]
+
+
 class HstuCastItem(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("numel", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32),
                 ("transpose", C.c_int32)]
@@ -80,6 +90,8 @@ SIGNATURES = {
     "hstu_attn_bwd": (_int, [C.POINTER(HstuAttnBwdParams), _vp]),
     "hstu_attn_fwd_kernel_name": (_int, [C.POINTER(HstuAttnParams), C.c_char_p, C.c_size_t]),
     "hstu_attn_bwd_kernel_name": (_int, [C.POINTER(HstuAttnBwdParams), C.c_char_p, C.c_size_t]),
+    "hstu_attn_fwd_fp8": (_int, [C.POINTER(HstuAttnParams), C.POINTER(HstuFp8Descale), _vp]),
+    "hstu_jagged_quantize_fp8": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _int, _int, _vp]),
     "hstu_complete_cumsum": (_int, [_vp, _vp, _i64, _int, _vp]),
     "hstu_concat_2d_jagged": (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _int, _vp]),
     "hstu_split_2d_jagged": (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _int, _vp]),
@@ -224,7 +236,9 @@ def torch_dtype_code(dtype: torch.dtype) -> int:
         return HSTU_DTYPE_F16
     if dtype == torch.float32:
         return HSTU_DTYPE_F32
-    raise RuntimeError(f"HSTU HIP ops support bf16 / fp16 / fp32 tensors, got {dtype}")
+    if dtype == torch.float8_e4m3fn:
+        return HSTU_DTYPE_FP8_E4M3
+    raise RuntimeError(f"HSTU HIP ops support bf16 / fp16 / fp32 tensors (fp8 e4m3: attention forward), got {dtype}")
 
 
 def index_dtype_code(t: torch.Tensor) -> int:

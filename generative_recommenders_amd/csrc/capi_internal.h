@@ -90,4 +90,10 @@ inline int bias_table_bytes(int max_seq_len, int num_buckets) {
          (2 * ((max_seq_len + 32 + 3) / 4 * 4) * 4 + 8 * 4 + 15) / 16 * 16;   // + int32 offsets and their copy shifted by one (padded), one range flag per wave
 }
 constexpr int kDqScratchBytes = 8 * 4096;   // general backward, several key blocks: one [32 q][32 d] fp32 tile per wave
+
+// e4m3 attention forward (attn_fp8.hip): head dims multiples of 16 up to 128, instantiated at 64 (smaller ones zero-padded) and 128
+inline int fp8_head_dim(int d) { return (d <= 0 || d % 16) ? 0 : (d <= 64 ? 64 : (d <= 128 ? 128 : 0)); }
+int launch_attn_fwd_fp8(const HstuAttnParams& p, const HstuFp8Descale& ds, hipStream_t st);
+int launch_jagged_quantize_fp8(const void* x, int64_t rs, int64_t hs, void* x8, float* descale, const void* offsets, int batch, int heads,
+                               int dim, int dtype, int index_dtype, hipStream_t st);
 }  // namespace hstu

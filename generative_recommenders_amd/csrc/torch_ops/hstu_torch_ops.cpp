@@ -30,7 +30,8 @@ static int dtype_code(const Tensor& t) {
     case at::kBFloat16: return HSTU_DTYPE_BF16;
     case at::kHalf: return HSTU_DTYPE_F16;
     case at::kFloat: return HSTU_DTYPE_F32;
-    default: TORCH_CHECK(false, "HSTU HIP ops support bf16 / fp16 / fp32 tensors, got ", t.scalar_type());
+    case at::kFloat8_e4m3fn: return HSTU_DTYPE_FP8_E4M3;   // attention forward only (bf16 out)
+    default: TORCH_CHECK(false, "HSTU HIP ops support bf16 / fp16 / fp32 tensors (fp8 e4m3: attention forward), got ", t.scalar_type());
   }
 }
 static Tensor index_tensor(const Tensor& t) {
@@ -42,6 +43,8 @@ static int index_code(const Tensor& t) { return t.scalar_type() == at::kLong ? H
 // head dims that are not a multiple of the 16-byte vector are zero-padded (zeros change neither q.k nor the sliced output)
 static Tensor pad_head_dim(const Tensor& t) {
   const int64_t mult = 16 / t.element_size(), pad = (mult - t.size(-1) % mult) % mult;
+  if (pad && t.scalar_type() == at::kFloat8_e4m3fn)   // (through its bytes: e4m3 zero is the zero byte)
+    return at::constant_pad_nd(t.view(at::kByte), {0, pad}).view(at::kFloat8_e4m3fn);
   return pad ? at::constant_pad_nd(t, {0, pad}) : t;
 }
 // (rows, H, d) with contiguous last dim and 16-byte aligned (row, head) vectors; copies only when the layout forces it
@@ -113,15 +116,42 @@ static void fill(HstuAttnParams& p, const Tensor& q, const Tensor& k, const Tens
   }
 }
 
-static void reject_fp8(const OptT& a, const OptT& b, const OptT& c) {
-  TORCH_CHECK(!a.has_value() && !b.has_value() && !c.has_value(), "hstu_mha: fp8 descale tensors are not supported on gfx950 (no fp8 instantiation)");
+static bool is_fp8(const Tensor& t) { return t.scalar_type() == at::kFloat8_e4m3fn; }
+
+// fp8 (e4m3) q / k / v: the forward only, bf16 output, per-(user, head) descales (flash_common.cpp:222-305, 448-536).  Descales
+// belong to fp8 inputs only; q / k / v of one dtype; dqk == dv (the reference's qk_d == v_d); no relative bias in this op.
+static void check_fp8_args(const Tensor& q, const Tensor& k, const Tensor& v, const OptT& qd, const OptT& kd, const OptT& vd) {
+  const bool any8 = is_fp8(q) || is_fp8(k) || is_fp8(v);
+  if (!any8) {
+    TORCH_CHECK(!qd.has_value() && !kd.has_value() && !vd.has_value(),
+                "hstu_mha_fwd: q_descale / k_descale / v_descale belong to fp8 (e4m3) q, k, v; got ", q.scalar_type(), " inputs");
+    return;
+  }
+  TORCH_CHECK(is_fp8(q) && is_fp8(k) && is_fp8(v), "hstu_mha_fwd: fp8 attention needs q, k, v all float8_e4m3fn, got ", q.scalar_type(),
+              ", ", k.scalar_type(), ", ", v.scalar_type());
+  TORCH_CHECK(q.size(-1) == k.size(-1) && k.size(-1) == v.size(-1), "hstu_mha_fwd: fp8 attention needs dqk == dv, got ", q.size(-1), " and ",
+              v.size(-1));
+  TORCH_CHECK(q.size(-1) <= 128, "hstu_mha_fwd: fp8 head dims above 128 are not instantiated, got ", q.size(-1));
+}
+
+// (B, H) fp32 GPU descale -> pointer + strides (kept as given: the reference checks the shape and keeps the strides)
+static void fill_descale(const OptT& t, const char* name, const Tensor& q, int64_t B, int64_t H, const float*& ptr, int64_t& sb,
+                         int64_t& sh) {
+  if (!t.has_value()) return;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->dim() == 2 && t->size(0) == B && t->size(1) == H, "hstu_mha_fwd: fp8 ",
+              name, " must be an fp32 (", B, ", ", H, ") GPU tensor, got ", t->scalar_type(), " ", t->sizes());
+  TORCH_CHECK(t->device() == q.device(), "hstu_mha_fwd: fp8 ", name, " is on ", t->device(), ", q on ", q.device());
+  ptr = (const float*)t->data_ptr();
+  sb = t->stride(0);
+  sh = t->stride(1);
 }
 
 Tensor hstu_mha_fwd(const at::SymInt max_seq_len_s, double alpha, Tensor& q, Tensor& k, Tensor& v, const OptT& seq_offsets, bool causal,
                     const OptT& num_targets, const OptT& attn_scale, int64_t max_attn_len, int64_t min_full_attn_seq_len,
                     int64_t contextual_seq_len, const OptT& q_descale, const OptT& k_descale, const OptT& v_descale,
                     const int64_t sm_margin) {
-  reject_fp8(q_descale, k_descale, v_descale);
+  check_fp8_args(q, k, v, q_descale, k_descale, v_descale);
+  const bool fp8 = is_fp8(q);
   TORCH_CHECK(causal, "only support causal attention");
   const int64_t N = max_seq_len_s.expect_int();
   TORCH_CHECK(N > 0, "max_seq_len must be larger than 0");
@@ -129,13 +159,20 @@ Tensor hstu_mha_fwd(const at::SymInt max_seq_len_s, double alpha, Tensor& q, Ten
   Jagged j = as_jagged(q, k, v, seq_offsets, N);
   const int64_t dv = j.v.size(2);
   Tensor qp = aligned_rows(pad_head_dim(j.q)), kp = aligned_rows(pad_head_dim(j.k)), vp = aligned_rows(pad_head_dim(j.v));
-  Tensor out = at::empty({qp.size(0), qp.size(1), vp.size(2)}, qp.options());
+  Tensor out = at::empty({qp.size(0), qp.size(1), vp.size(2)}, fp8 ? qp.options().dtype(at::kBFloat16) : qp.options());
+  HstuFp8Descale ds;
+  memset(&ds, 0, sizeof(ds));
+  if (fp8) {
+    fill_descale(q_descale, "q_descale", qp, j.B, qp.size(1), ds.q, ds.q_batch_stride, ds.q_head_stride);
+    fill_descale(k_descale, "k_descale", qp, j.B, qp.size(1), ds.k, ds.k_batch_stride, ds.k_head_stride);
+    fill_descale(v_descale, "v_descale", qp, j.B, qp.size(1), ds.v, ds.v_batch_stride, ds.v_head_stride);
+  }
   if (qp.size(0) > 0) {
     HstuAttnParams p;
     Tensor nt_keep, scale_keep;
     fill(p, qp, kp, vp, j.offsets, num_targets, nt_keep, N, alpha, attn_scale, scale_keep, max_attn_len, min_full_attn_seq_len, contextual_seq_len);
     p.out = out.data_ptr(); p.o_row_stride = out.stride(0); p.o_head_stride = out.stride(1);
-    check(hstu_attn_fwd(&p, stream_of(qp)), "hstu_mha_fwd");
+    check(fp8 ? hstu_attn_fwd_fp8(&p, &ds, stream_of(qp)) : hstu_attn_fwd(&p, stream_of(qp)), "hstu_mha_fwd");
   }
   if (out.size(2) != dv) out = out.slice(2, 0, dv).contiguous();
   return j.dense ? out.reshape({j.B, j.S, out.size(1), out.size(2)}) : out;
@@ -145,6 +182,7 @@ std::vector<Tensor> hstu_mha_bwd(int64_t max_seq_len, double alpha, Tensor& dout
                                  Tensor& dv, const OptT& seq_offsets, bool causal, const OptT& num_targets, const OptT& attn_scale,
                                  int64_t max_attn_len, int64_t min_full_attn_seq_len, int64_t contextual_seq_len, bool sort_by_length,
                                  bool deterministic, const int64_t sm_margin) {
+  TORCH_CHECK(!is_fp8(q) && !is_fp8(k) && !is_fp8(v), "hstu_mha_bwd: fp8 (e4m3) attention is forward-only; there is no fp8 backward");
   TORCH_CHECK(causal, "only support causal attention");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
   Jagged j = as_jagged(q, k, v, seq_offsets, max_seq_len);
@@ -216,6 +254,7 @@ class HstuMhaFunction : public torch::autograd::Function<HstuMhaFunction> {
     static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("hstu::hstu_mha_bwd", "").typed<decltype(hstu_mha_bwd)>();
     auto saved = ctx->get_saved_variables();
     Tensor q = saved[0], k = saved[1], v = saved[2];
+    TORCH_CHECK(!is_fp8(q), "hstu_mha: fp8 (e4m3) attention is forward-only; there is no fp8 backward");
     auto opt = [](const Tensor& t) { return t.defined() ? OptT(t) : std::nullopt; };
     Tensor dout = grads[0].contiguous();
     Tensor dq = at::empty_like(q), dk = at::empty_like(k), dv = at::empty_like(v);
@@ -252,8 +291,9 @@ Tensor hstu_mha(const at::SymInt max_seq_len, double alpha, const Tensor& q, con
 static Tensor fwd_out_meta(const at::SymInt& max_seq_len, const Tensor& q, const Tensor& v, const OptT& seq_offsets) {
   auto qs = q.sym_sizes();
   auto vd = v.sym_sizes().back();
-  if (seq_offsets.has_value()) return at::empty_symint({qs[0], qs[1], vd}, q.options());
-  return at::empty_symint({qs[0], max_seq_len, qs[2], vd}, q.options());
+  const auto opts = q.scalar_type() == at::kFloat8_e4m3fn ? q.options().dtype(at::kBFloat16) : q.options();   // fp8 in, bf16 out
+  if (seq_offsets.has_value()) return at::empty_symint({qs[0], qs[1], vd}, opts);
+  return at::empty_symint({qs[0], max_seq_len, qs[2], vd}, opts);
 }
 Tensor hstu_mha_fwd_meta(const at::SymInt max_seq_len, double, Tensor& q, Tensor&, Tensor& v, const OptT& seq_offsets, bool, const OptT&, const OptT&,
                          int64_t, int64_t, int64_t, const OptT&, const OptT&, const OptT&, const int64_t) {

@@ -119,14 +119,18 @@ def _fill_attn_params(p: L.HstuAttnParams, q, k, v, out, seq_offsets, num_target
 
 
 def attn_fwd(q, k, v, seq_offsets, num_targets, max_seq_len, alpha, scale, max_attn_len=0,
-             contextual_seq_len=0, min_full_attn_seq_len=0, delta_q=0, user_order=None) -> torch.Tensor:
+             contextual_seq_len=0, min_full_attn_seq_len=0, delta_q=0, user_order=None, descales=None) -> torch.Tensor:
+    """``descales``: fp8 (e4m3) q / k / v only -- (q_descale, k_descale, v_descale), each None (= 1) or an fp32 (B, H) GPU
+    tensor with any strides (hstu_attn_fwd_fp8)."""
     for name, t in (("q", q), ("k", k), ("v", v), ("seq_offsets", seq_offsets)):
         L.require_gpu_tensor(t, name)
     if not (q.dtype == k.dtype == v.dtype):
         raise RuntimeError("q, k, v must have the same dtype")
     q, k, v = _aligned_rows(q), _aligned_rows(k), _aligned_rows(v)
     seq_offsets, num_targets = _idx(seq_offsets), _idx(num_targets)
-    out = torch.empty((q.shape[0], q.shape[1], v.shape[2]), dtype=q.dtype, device=q.device)
+    # fp8 (e4m3) q / k / v: bf16 output, as the reference's fp8 forward (flash_common.cpp:454)
+    out_dtype = torch.bfloat16 if q.dtype == torch.float8_e4m3fn else q.dtype
+    out = torch.empty((q.shape[0], q.shape[1], v.shape[2]), dtype=out_dtype, device=q.device)
     if q.shape[0] == 0:
         return out
     if DEBUG_CHECKS:
@@ -135,8 +139,56 @@ def attn_fwd(q, k, v, seq_offsets, num_targets, max_seq_len, alpha, scale, max_a
     _fill_attn_params(p, q, k, v, out, seq_offsets, num_targets, max_seq_len, alpha, scale, max_attn_len,
                       contextual_seq_len, min_full_attn_seq_len, delta_q, user_order)
     with torch.cuda.device(q.device):
-        L.check(L.lib().hstu_attn_fwd(C.byref(p), L.current_stream_ptr(q.device)))
+        if descales is None:
+            L.check(L.lib().hstu_attn_fwd(C.byref(p), L.current_stream_ptr(q.device)))
+        else:
+            L.check(L.lib().hstu_attn_fwd_fp8(C.byref(p), C.byref(_fp8_descale(descales, p.batch, p.heads, q.device)),
+                                              L.current_stream_ptr(q.device)))
     return out
+
+
+def _fp8_descale(descales, batch: int, heads: int, device) -> "L.HstuFp8Descale":
+    """(q, k, v) descale tensors, each None or fp32 (batch, heads) on q's GPU with any strides -> HstuFp8Descale"""
+    d = L.HstuFp8Descale()
+    for name, t in zip("qkv", descales):
+        if t is None:
+            continue
+        L.require_gpu_tensor(t, f"{name}_descale")
+        if t.dtype != torch.float32 or tuple(t.shape) != (batch, heads):
+            raise RuntimeError(f"fp8 attention: {name}_descale must be an fp32 ({batch}, {heads}) tensor, got {t.dtype} {tuple(t.shape)}")
+        if t.device != device:
+            raise RuntimeError(f"fp8 attention: {name}_descale is on {t.device}, q on {device}")
+        setattr(d, name, t.data_ptr())
+        setattr(d, f"{name}_batch_stride", t.stride(0))
+        setattr(d, f"{name}_head_stride", t.stride(1))
+    return d
+
+
+def jagged_quantize_fp8(x: torch.Tensor, seq_offsets: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(x8, descale) of a jagged (rows, H, d) bf16 / fp16 / fp32 tensor (hstu_jagged_quantize_fp8): x8 contiguous e4m3, descale
+    fp32 (B, H)"""
+    L.require_gpu_tensor(x, "x")
+    L.require_gpu_tensor(seq_offsets, "seq_offsets")
+    if x.dim() != 3 or x.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        raise RuntimeError(f"quantize_jagged_fp8: x must be a (rows, heads, dim) bf16 / fp16 / fp32 tensor, got {x.dtype} {tuple(x.shape)}")
+    if x.stride(2) != 1:
+        x = x.contiguous()
+    seq_offsets = _idx(seq_offsets)
+    if seq_offsets.device != x.device:
+        raise RuntimeError(f"quantize_jagged_fp8: seq_offsets is on {seq_offsets.device}, x on {x.device}")
+    B, H, d = seq_offsets.numel() - 1, x.shape[1], x.shape[2]
+    if DEBUG_CHECKS and B > 0:   # (the kernel reads and writes the rows the offsets name: one host sync, debugging only)
+        if bool((seq_offsets[1:] < seq_offsets[:-1]).any()) or int(seq_offsets[0]) < 0 or int(seq_offsets[-1]) > x.shape[0]:
+            raise RuntimeError(f"quantize_jagged_fp8: seq_offsets must be non-decreasing within [0, {x.shape[0]}] (the rows of x)")
+    x8 = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
+    descale = torch.empty((B, H), dtype=torch.float32, device=x.device)
+    if B == 0 or x8.numel() == 0:
+        return x8, descale.fill_(1.0)
+    with torch.cuda.device(x.device):
+        L.check(L.lib().hstu_jagged_quantize_fp8(x.data_ptr(), x.stride(0), x.stride(1), x8.data_ptr(), descale.data_ptr(),
+                                                 seq_offsets.data_ptr(), B, H, d, L.torch_dtype_code(x.dtype),
+                                                 L.index_dtype_code(seq_offsets), L.current_stream_ptr(x.device)))
+    return x8, descale
 
 
 def attn_bwd(dout, q, k, v, seq_offsets, num_targets, max_seq_len, alpha, scale, max_attn_len=0,

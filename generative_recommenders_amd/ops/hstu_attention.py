@@ -24,6 +24,8 @@ def _pad_head_dim(t: torch.Tensor) -> torch.Tensor:
     ML-1M configs) are zero-padded; zeros change neither q.k nor the sliced output."""
     mult = 16 // t.element_size()
     pad = (-t.shape[-1]) % mult
+    if pad and t.dtype == torch.float8_e4m3fn:   # (padded through its bytes: e4m3 zero is the zero byte)
+        return F.pad(t.view(torch.uint8), (0, pad)).view(torch.float8_e4m3fn)
     return F.pad(t, (0, pad)) if pad else t
 
 
@@ -50,6 +52,8 @@ class _HstuMhaFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         q, k, v, seq_offsets = ctx.saved_tensors[:4]
+        if q.dtype == torch.float8_e4m3fn:
+            raise RuntimeError("hstu_mha: fp8 (e4m3) attention is forward-only; there is no fp8 backward")
         num_targets = ctx.saved_tensors[4] if ctx.has_targets else None
         max_seq_len, alpha, max_attn_len, contextual_seq_len, min_full = ctx.args
         if _PRECISE and q.dtype in (torch.bfloat16, torch.float16):

@@ -36,7 +36,8 @@ enum {
   HSTU_ELAUNCH = -3,     /* HIP launch error */
 };
 
-enum { HSTU_DTYPE_BF16 = 0, HSTU_DTYPE_F16 = 1, HSTU_DTYPE_F32 = 2 };
+/* HSTU_DTYPE_FP8_E4M3: attention forward only -- q, k, v are OCP e4m3fn (torch.float8_e4m3fn), out is bf16 */
+enum { HSTU_DTYPE_BF16 = 0, HSTU_DTYPE_F16 = 1, HSTU_DTYPE_F32 = 2, HSTU_DTYPE_FP8_E4M3 = 3 };
 enum { HSTU_INDEX_I32 = 0, HSTU_INDEX_I64 = 1 };
 
 /*
@@ -153,6 +154,37 @@ int hstu_attn_bwd(const HstuAttnBwdParams* p, void* stream);
  * dispatcher branches (ops/hstu_attention.py:87-128, flash_common.cpp:496-507). */
 int hstu_attn_fwd_kernel_name(const HstuAttnParams* p, char* buf, size_t len);
 int hstu_attn_bwd_kernel_name(const HstuAttnBwdParams* p, char* buf, size_t len);
+
+/*
+ * fp8 attention forward (dtype == HSTU_DTYPE_FP8_E4M3): the e4m3 path of hstu::hstu_mha_fwd
+ * (ops/cpp/hstu_attention/flash_common.cpp:222-305, 448-536).  q, k, v are e4m3 (row / head strides in ELEMENTS = bytes,
+ * 16-byte aligned vectors), out is bf16 (strides in bf16 elements).  Per user b and head h:
+ *   out[i,h,:] = sum_j silu(alpha qd kd <q_i,k_j>) * scale * M[i,j] * vd * v_j
+ * with qd = q[b * q_batch_stride + h * q_head_stride] (fp32, device) and likewise kd, vd; a NULL pointer means 1.  The
+ * reference's kernels load these descales but never apply them; here they are applied.  dqk == dv, multiples of 16, <= 128
+ * (64 and 128 instantiated, smaller heads zero-padded to 64); every mask option, attn_scale, user_order and delta_q > 0;
+ * no relative bias (pos_w must be NULL).  hstu_attn_fwd takes HSTU_DTYPE_FP8_E4M3 too (all descales 1); the backward
+ * entry points answer HSTU_EUNSUPPORTED for it.
+ */
+typedef struct HstuFp8Descale {
+  const float* q;
+  const float* k;
+  const float* v;
+  int64_t q_batch_stride, q_head_stride;
+  int64_t k_batch_stride, k_head_stride;
+  int64_t v_batch_stride, v_head_stride;
+} HstuFp8Descale;
+int hstu_attn_fwd_fp8(const HstuAttnParams* p, const HstuFp8Descale* descale, void* stream);
+
+/* Per-(user, head) e4m3 quantizer of a jagged (total_rows, heads, dim) tensor x (bf16 / fp16 / fp32 `dtype`, row / head
+ * strides in elements, last dim contiguous -- e.g. a view of the fused uvqk buffer):
+ *   descale[b * heads + h] = amax over user b's rows of head h of |x| / 448   (1 when that amax is 0)
+ *   x8[r, h, c] = e4m3(clamp(x[r, h, c] / descale[b, h], -448, 448))          (IEEE division, round to nearest even)
+ * x8 is a contiguous (total_rows, heads, dim) e4m3 array, descale a contiguous (batch, heads) fp32 array.  The caller has no
+ * other way to form per-user amaxes of a jagged tensor. */
+int hstu_jagged_quantize_fp8(const void* x, int64_t x_row_stride, int64_t x_head_stride, void* x8, float* descale,
+                             const void* seq_offsets, int32_t batch, int32_t heads, int32_t dim, int dtype, int index_dtype,
+                             void* stream);
 
 /* out[0] = 0, out[i+1] = sum(in[0..i]); n elements in, n+1 out; dtype preserved.
  * Replaces hstu::complete_cumsum (ops/cpp/complete_cumsum.cu:7-47) and
