@@ -92,6 +92,11 @@ SIGNATURES = {
     "hstu_attn_bwd_kernel_name": (_int, [C.POINTER(HstuAttnBwdParams), C.c_char_p, C.c_size_t]),
     "hstu_attn_fwd_fp8": (_int, [C.POINTER(HstuAttnParams), C.POINTER(HstuFp8Descale), _vp]),
     "hstu_jagged_quantize_fp8": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _int, _int, _vp]),
+    "hstu_jagged_dense_bmm_workspace_bytes": (C.c_size_t, [_i32]),
+    "hstu_jagged_dense_bmm_fwd": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp,
+                                         _int, _int, _vp]),
+    "hstu_jagged_dense_bmm_wgrad": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _int,
+                                           _int, _vp]),
     "hstu_complete_cumsum": (_int, [_vp, _vp, _i64, _int, _vp]),
     "hstu_concat_2d_jagged": (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _int, _vp]),
     "hstu_split_2d_jagged": (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _int, _vp]),

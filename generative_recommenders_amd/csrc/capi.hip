@@ -4,6 +4,8 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <initializer_list>
+
 #include "capi_internal.h"
 
 namespace hstu {
@@ -180,6 +182,72 @@ int hstu_jagged_quantize_fp8(const void* x, int64_t x_row_stride, int64_t x_head
   if (batch == 0) return HSTU_OK;
   return launch_jagged_quantize_fp8(x, x_row_stride, x_head_stride, x8, descale, seq_offsets, batch, heads, dim, dtype, index_dtype,
                                     (hipStream_t)stream);
+}
+
+// shared checks of the two jagged_dense_bmm entry points (shape and type codes first: they need no pointer)
+static int validate_bmm_shape(const char* who, int64_t total_rows, int32_t batch, int32_t k, int32_t n, int dtype, int index_dtype) {
+  if (dtype != HSTU_DTYPE_BF16 && dtype != HSTU_DTYPE_F16 && dtype != HSTU_DTYPE_F32)
+    return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32 (got code %d)", who, dtype);
+  if (index_dtype != HSTU_INDEX_I32 && index_dtype != HSTU_INDEX_I64)
+    return set_error(HSTU_EINVAL, "%s: seq_offsets must be int32 or int64 (got code %d)", who, index_dtype);
+  if (k <= 0 || n <= 0) return set_error(HSTU_EINVAL, "%s: K and N must be positive (got %d, %d)", who, k, n);
+  if (batch < 0 || total_rows < 0) return set_error(HSTU_EINVAL, "%s: negative batch / total_rows", who);
+  const int epu = dtype == HSTU_DTYPE_F32 ? 4 : 8;
+  if (k % epu || n % epu)
+    return set_error(HSTU_EINVAL, "%s: K and N (%d, %d) must be multiples of %d elements (16 bytes); zero-pad them", who, k, n, epu);
+  return HSTU_OK;
+}
+
+static bool bmm_aligned(int eb, const void* p, std::initializer_list<int64_t> strides) {
+  if ((uintptr_t)p & 15) return false;
+  for (int64_t s : strides)
+    if ((s * eb) % 16) return false;
+  return true;
+}
+
+size_t hstu_jagged_dense_bmm_workspace_bytes(int32_t batch) { return jagged_bmm_workspace_bytes(batch); }
+
+int hstu_jagged_dense_bmm_fwd(const void* jagged, int64_t jagged_row_stride, const void* dense, int64_t dense_batch_stride,
+                              int64_t dense_k_stride, int64_t dense_n_stride, const float* bias, int64_t bias_batch_stride,
+                              void* out, int64_t out_row_stride, const void* seq_offsets, int64_t total_rows, int32_t batch,
+                              int32_t k, int32_t n, void* workspace, int dtype, int index_dtype, void* stream) {
+  const char* who = "hstu_jagged_dense_bmm_fwd";
+  if (int e = validate_bmm_shape(who, total_rows, batch, k, n, dtype, index_dtype)) return e;
+  if (batch == 0 || total_rows == 0) return HSTU_OK;
+  if (!jagged || !dense || !out || !seq_offsets || !workspace)
+    return set_error(HSTU_EINVAL, "%s: jagged, dense, out, seq_offsets and workspace must be non-NULL", who);
+  const int eb = dtype == HSTU_DTYPE_F32 ? 4 : 2;
+  if (dense_n_stride != 1 && dense_k_stride != 1)
+    return set_error(HSTU_EINVAL, "%s: dense needs a unit stride along K or N (got %lld, %lld)", who, (long long)dense_k_stride,
+                     (long long)dense_n_stride);
+  if (jagged_row_stride < k || out_row_stride < n) return set_error(HSTU_EINVAL, "%s: a row stride is smaller than a row", who);
+  if (!bmm_aligned(eb, jagged, {jagged_row_stride}) || !bmm_aligned(eb, out, {out_row_stride}) ||
+      !bmm_aligned(eb, dense, {dense_batch_stride, dense_n_stride == 1 ? dense_k_stride : dense_n_stride}) ||
+      ((uintptr_t)workspace & 3) || (bias && ((uintptr_t)bias & 3)))
+    return set_error(HSTU_EINVAL, "%s: rows of jagged, dense and out must start 16-byte aligned", who);
+  return launch_jagged_bmm_fwd(jagged, jagged_row_stride, dense, dense_batch_stride, dense_k_stride, dense_n_stride, bias,
+                               bias_batch_stride, out, out_row_stride, seq_offsets, total_rows, batch, k, n, workspace, dtype,
+                               index_dtype, (hipStream_t)stream);
+}
+
+int hstu_jagged_dense_bmm_wgrad(const void* jagged, int64_t jagged_row_stride, const void* d_out, int64_t d_out_row_stride,
+                                void* d_dense, int64_t d_dense_batch_stride, int64_t d_dense_k_stride, float* d_bias,
+                                int64_t d_bias_batch_stride, const void* seq_offsets, int64_t total_rows, int32_t batch, int32_t k,
+                                int32_t n, int dtype, int index_dtype, void* stream) {
+  const char* who = "hstu_jagged_dense_bmm_wgrad";
+  if (int e = validate_bmm_shape(who, total_rows, batch, k, n, dtype, index_dtype)) return e;
+  if (batch == 0) return HSTU_OK;
+  if (!d_dense || !seq_offsets || (total_rows > 0 && (!jagged || !d_out)))
+    return set_error(HSTU_EINVAL, "%s: jagged, d_out, d_dense and seq_offsets must be non-NULL", who);
+  const int eb = dtype == HSTU_DTYPE_F32 ? 4 : 2;
+  if ((total_rows > 0 && (jagged_row_stride < k || d_out_row_stride < n)) || d_dense_k_stride < n)
+    return set_error(HSTU_EINVAL, "%s: a row stride is smaller than a row", who);
+  if ((total_rows > 0 && (!bmm_aligned(eb, jagged, {jagged_row_stride}) || !bmm_aligned(eb, d_out, {d_out_row_stride}))) ||
+      !bmm_aligned(eb, d_dense, {d_dense_batch_stride, d_dense_k_stride}) || (d_bias && ((uintptr_t)d_bias & 3)))
+    return set_error(HSTU_EINVAL, "%s: rows of jagged, d_out and d_dense must start 16-byte aligned", who);
+  return launch_jagged_bmm_wgrad(jagged, jagged_row_stride, d_out, d_out_row_stride, d_dense, d_dense_batch_stride,
+                                 d_dense_k_stride, d_bias, d_bias_batch_stride, seq_offsets, total_rows, batch, k, n, dtype,
+                                 index_dtype, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -96,4 +96,14 @@ inline int fp8_head_dim(int d) { return (d <= 0 || d % 16) ? 0 : (d <= 64 ? 64 :
 int launch_attn_fwd_fp8(const HstuAttnParams& p, const HstuFp8Descale& ds, hipStream_t st);
 int launch_jagged_quantize_fp8(const void* x, int64_t rs, int64_t hs, void* x8, float* descale, const void* offsets, int batch, int heads,
                                int dim, int dtype, int index_dtype, hipStream_t st);
+
+// jagged_dense_bmm_broadcast_add (jagged_bmm.hip): forward / data gradient and weight + bias gradient; arguments as validated by capi.hip
+size_t jagged_bmm_workspace_bytes(int batch);
+int launch_jagged_bmm_fwd(const void* jagged, int64_t a_rs, const void* dense, int64_t d_bs, int64_t d_ks, int64_t d_ns,
+                          const float* bias, int64_t bias_bs, void* out, int64_t o_rs, const void* offsets,
+                          int64_t total_rows, int batch, int k, int n, void* workspace, int dtype, int index_dtype,
+                          hipStream_t st);
+int launch_jagged_bmm_wgrad(const void* jagged, int64_t a_rs, const void* d_out, int64_t g_rs, void* d_dense, int64_t dd_bs,
+                            int64_t dd_ks, float* d_bias, int64_t db_bs, const void* offsets, int64_t total_rows, int batch,
+                            int k, int n, int dtype, int index_dtype, hipStream_t st);
 }  // namespace hstu

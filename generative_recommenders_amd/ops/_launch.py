@@ -406,6 +406,99 @@ def concat_1d_jagged_jagged(lengths_left, values_left, lengths_right, values_rig
     return out
 
 
+# ----------------------------------------------------------------------------- jagged x dense bmm
+def _bmm_unit(dtype: torch.dtype) -> int:
+    return 4 if dtype == torch.float32 else 8      # elements per 16 bytes
+
+
+def _bmm_rows(t: torch.Tensor, cols: int) -> torch.Tensor:
+    """(rows, c) -> (rows, cols >= c) with unit column stride and 16-byte aligned rows; zero-padded copy only when needed"""
+    es = t.element_size()
+    if t.shape[1] == cols and t.stride(1) == 1 and (t.stride(0) * es) % 16 == 0 and t.stride(0) >= cols and t.data_ptr() % 16 == 0:
+        return t
+    if t.shape[1] == cols:
+        return t.contiguous()
+    return torch.nn.functional.pad(t, (0, cols - t.shape[1]))
+
+
+def _bmm_dense(d: torch.Tensor, kp: int, np_: int) -> torch.Tensor:
+    """(B, K, N) -> (B, kp, np_) the kernel can read: a unit stride along K or N, the other strides multiples of 16 bytes"""
+    es = d.element_size()
+    ok = d.shape[1] == kp and d.shape[2] == np_ and d.data_ptr() % 16 == 0 and (d.stride(0) * es) % 16 == 0
+    if ok and d.stride(2) == 1 and (d.stride(1) * es) % 16 == 0:
+        return d
+    if ok and d.stride(1) == 1 and (d.stride(2) * es) % 16 == 0:
+        return d
+    if d.shape[1] == kp and d.shape[2] == np_:
+        return d.contiguous()
+    return torch.nn.functional.pad(d, (0, np_ - d.shape[2], 0, kp - d.shape[1]))
+
+
+def _bmm_check(jagged, dense, seq_offsets, what):
+    L.require_gpu_tensor(jagged, what)
+    L.require_gpu_tensor(dense, "dense")
+    L.require_gpu_tensor(seq_offsets, "seq_offsets")
+    if jagged.dtype not in (torch.bfloat16, torch.float16, torch.float32) or dense.dtype != jagged.dtype:
+        raise RuntimeError(f"jagged_dense_bmm: {what} and dense must share a bf16 / fp16 / fp32 dtype, got {jagged.dtype} and {dense.dtype}")
+    if dense.device != jagged.device or seq_offsets.device != jagged.device:
+        raise RuntimeError(f"jagged_dense_bmm: {what} is on {jagged.device}, dense on {dense.device}, seq_offsets on {seq_offsets.device}")
+
+
+def jagged_dense_bmm_fwd(jagged: torch.Tensor, dense: torch.Tensor, bias: Optional[torch.Tensor],
+                         seq_offsets: torch.Tensor) -> torch.Tensor:
+    """out[s:e] = jagged[s:e] @ dense[b] (+ bias[b]) per user (hstu_jagged_dense_bmm_fwd).  jagged (rows, K), dense (B, K, N) with
+    any strides, bias (B, N) of any float dtype or None -> (rows, N).  The data gradient is this with d_out as ``jagged``,
+    ``dense.transpose(1, 2)`` and no bias.  K / N that are not multiples of 16 bytes are zero-padded here (exact)."""
+    _bmm_check(jagged, dense, seq_offsets, "jagged")
+    seq_offsets = _idx(seq_offsets)
+    rows, K = jagged.shape
+    B, _, N = dense.shape
+    unit = _bmm_unit(jagged.dtype)
+    kp, np_ = -(-K // unit) * unit, -(-N // unit) * unit
+    out = torch.empty((rows, np_), dtype=jagged.dtype, device=jagged.device)
+    if B > 0 and rows > 0:
+        a = _bmm_rows(jagged, kp)
+        d = _bmm_dense(dense, kp, np_)
+        bf = None
+        if bias is not None:
+            bf = _bmm_rows(bias.to(device=jagged.device, dtype=torch.float32), np_).contiguous()
+        lib = L.lib()
+        ws = torch.empty(lib.hstu_jagged_dense_bmm_workspace_bytes(B), dtype=torch.uint8, device=jagged.device)
+        with torch.cuda.device(jagged.device):
+            L.check(lib.hstu_jagged_dense_bmm_fwd(a.data_ptr(), a.stride(0), d.data_ptr(), d.stride(0), d.stride(1), d.stride(2),
+                                                  _vp(bf), np_, out.data_ptr(), out.stride(0), seq_offsets.data_ptr(), rows, B,
+                                                  kp, np_, ws.data_ptr(), L.torch_dtype_code(jagged.dtype),
+                                                  L.index_dtype_code(seq_offsets), L.current_stream_ptr(jagged.device)))
+    return out if np_ == N else out[:, :N].contiguous()
+
+
+def jagged_dense_bmm_wgrad(jagged: torch.Tensor, d_out: torch.Tensor, seq_offsets: torch.Tensor,
+                           want_bias: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(d_dense (B, K, N) in jagged's dtype, d_bias (B, N) fp32 or None) of jagged_dense_bmm_fwd (hstu_jagged_dense_bmm_wgrad):
+    fixed summation order, every slab written (zeros for an empty user)."""
+    _bmm_check(jagged, d_out, seq_offsets, "jagged")
+    seq_offsets = _idx(seq_offsets)
+    rows, K = jagged.shape
+    N = d_out.shape[1]
+    B = seq_offsets.numel() - 1
+    unit = _bmm_unit(jagged.dtype)
+    kp, np_ = -(-K // unit) * unit, -(-N // unit) * unit
+    dd = torch.empty((B, kp, np_), dtype=jagged.dtype, device=jagged.device)
+    db = torch.empty((B, np_), dtype=torch.float32, device=jagged.device) if want_bias else None
+    if B > 0:
+        a = _bmm_rows(jagged, kp)
+        g = _bmm_rows(d_out, np_)
+        with torch.cuda.device(jagged.device):
+            L.check(L.lib().hstu_jagged_dense_bmm_wgrad(a.data_ptr(), a.stride(0), g.data_ptr(), g.stride(0), dd.data_ptr(),
+                                                        dd.stride(0), dd.stride(1), _vp(db), np_, seq_offsets.data_ptr(), rows, B,
+                                                        kp, np_, L.torch_dtype_code(jagged.dtype),
+                                                        L.index_dtype_code(seq_offsets), L.current_stream_ptr(jagged.device)))
+    if kp != K or np_ != N:
+        dd = dd[:, :K, :N].contiguous()
+        db = db[:, :N].contiguous() if db is not None else None
+    return dd, db
+
+
 # ----------------------------------------------------------------------------- norms
 def _f32(n, device):
     return torch.empty(n, dtype=torch.float32, device=device)

@@ -1,6 +1,7 @@
 """Drop-in for generative_recommenders/ops/jagged_tensors.py (``concat_2D_jagged`` :55-90,
 ``split_2D_jagged`` :93-144, ``hstu_split_l2_embeddings`` :147-174,
-``hstu_concat_l2_embeddings`` :177-207) plus the fbgemm-style helpers the hot path uses
+``hstu_concat_l2_embeddings`` :177-207, ``jagged_dense_bmm_broadcast_add`` :210-253 -- a per-user MFMA GEMM along the
+offset vector, see csrc/jagged_bmm.hip) plus the fbgemm-style helpers the hot path uses
 (``jagged_to_padded_dense`` / ``dense_to_jagged`` / ``asynchronous_complete_cumsum``), all on
 the HIP row-copy kernels (bit-exact).  Backward of a concat is the split of the gradient
 and vice versa (cf. ops/triton/triton_jagged_tensors.py:145-359)."""
@@ -210,3 +211,53 @@ def expand_1d_jagged_to_dense(values: torch.Tensor, offsets: torch.Tensor, max_l
 def concat_1d_jagged_jagged(lengths_left, values_left, lengths_right, values_right) -> torch.Tensor:
     """hstu::concat_1d_jagged_jagged (ops/cpp/cpp_ops.cpp:94-102)."""
     return _launch.concat_1d_jagged_jagged(lengths_left, values_left, lengths_right, values_right)
+
+
+class _JaggedDenseBmmBroadcastAddFunction(torch.autograd.Function):
+    """autograd node of jagged_dense_bmm_broadcast_add (cf. ops/triton/triton_jagged.py:524-632): saves seq_offsets, jagged
+    and dense; the data gradient is the forward kernel on dense^T, the weight and bias gradients come out of one pass."""
+
+    @staticmethod
+    def forward(ctx, seq_offsets, jagged, dense, bias):
+        ctx.dense_dtype, ctx.bias_dtype = dense.dtype, bias.dtype
+        dense = dense.to(jagged.dtype)
+        ctx.save_for_backward(seq_offsets, jagged, dense)
+        return _launch.jagged_dense_bmm_fwd(jagged, dense, bias, seq_offsets)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        seq_offsets, jagged, dense = ctx.saved_tensors
+        need_j, need_d, need_b = ctx.needs_input_grad[1:4]
+        d_out = d_out.to(jagged.dtype)
+        d_jagged = d_dense = d_bias = None
+        if need_j:
+            d_jagged = _launch.jagged_dense_bmm_fwd(d_out, dense.transpose(1, 2), None, seq_offsets)
+        if need_d or need_b:
+            d_dense, d_bias = _launch.jagged_dense_bmm_wgrad(jagged, d_out, seq_offsets, want_bias=need_b)
+            d_dense = d_dense.to(ctx.dense_dtype) if need_d else None
+            d_bias = d_bias.to(ctx.bias_dtype) if need_b else None
+        return None, d_jagged, d_dense, d_bias
+
+
+def jagged_dense_bmm_broadcast_add(
+    max_seq_len: int,
+    seq_offsets: torch.Tensor,
+    jagged: torch.Tensor,
+    dense: torch.Tensor,
+    bias: torch.Tensor,
+    kernel: HammerKernel = HammerKernel.HIP,
+) -> torch.Tensor:
+    """out = jagged x dense + bias per user: jagged (sum_B(M_i), K), dense (B, K, N), bias (B, N) -> (sum_B(M_i), N), with
+    fp32 accumulation and one rounding to jagged's dtype; gradients for jagged, dense and bias in their own dtypes.
+
+    ``max_seq_len`` sizes nothing here: every row the offsets name is computed.  A user longer than ``max_seq_len`` is
+    outside the reference's contract (its padded path truncates such a user, its Triton path leaves the rows unwritten);
+    this op computes all of its rows."""
+    _, K = jagged.shape
+    B, _, N = dense.shape
+    torch._assert(dense.shape[1] == K, "wrong dense shape[1]")
+    torch._assert(seq_offsets.shape[0] == B + 1, "wrong seq_offsets shape[0]")
+    torch._assert(bias.shape[0] == B, "wrong bias shape[0]")
+    torch._assert(bias.shape[1] == N, "wrong bias shape[1]")
+    del kernel, max_seq_len
+    return _JaggedDenseBmmBroadcastAddFunction.apply(seq_offsets, jagged, dense, bias)

@@ -457,6 +457,32 @@ int hstu_column_sum(const void* x, int64_t ldx, int64_t rows, int32_t cols, floa
 int hstu_calib_mfma_stream(int32_t iters, float* sink, double* flops, void* stream);
 int hstu_calib_read_stream(const void* src, size_t bytes, float* sink, void* stream);
 
+/* ---- jagged_dense_bmm_broadcast_add: a per-user GEMM along the offset vector ------------------------------
+ * For user b with rows [s, e) = [seq_offsets[b], seq_offsets[b+1]):
+ *   out[s:e] = jagged[s:e] @ dense[b] + bias[b]      fp32 accumulation, one rounding to `dtype`
+ * Replaces jagged_dense_bmm_broadcast_add (ops/jagged_tensors.py:210-253; ops/pytorch/pt_jagged.py:77-98, a padded
+ * torch.bmm; ops/triton/triton_jagged.py:61-142 and the autograd node :524-632).  jagged (total_rows, K) and out
+ * (total_rows, N) in `dtype` with a row stride in elements and unit column stride; dense (batch, K, N) in `dtype`
+ * through three strides, one of dense_k_stride / dense_n_stride being 1 (both storage orders give bit-identical
+ * results); bias (batch, N) fp32, or NULL for no bias.  The DATA GRADIENT is the same call with d_out as `jagged`,
+ * dense's K / N strides (and k / n) swapped and bias = NULL (triton_jagged.py:588-605).  k and n are multiples of 16
+ * bytes, every row starts 16-byte aligned (zero-pad what is not).  Rows come from the offsets, not from a max_seq_len:
+ * there is none.  `workspace`: hstu_jagged_dense_bmm_workspace_bytes(batch) bytes of device memory (the users' tile
+ * offsets, int32).  Offsets are clamped to [0, total_rows].  batch == 0 or total_rows == 0 returns without a launch. */
+size_t hstu_jagged_dense_bmm_workspace_bytes(int32_t batch);
+int hstu_jagged_dense_bmm_fwd(const void* jagged, int64_t jagged_row_stride, const void* dense, int64_t dense_batch_stride,
+                              int64_t dense_k_stride, int64_t dense_n_stride, const float* bias, int64_t bias_batch_stride,
+                              void* out, int64_t out_row_stride, const void* seq_offsets, int64_t total_rows, int32_t batch,
+                              int32_t k, int32_t n, void* workspace, int dtype, int index_dtype, void* stream);
+/* d_dense[b] = jagged[s:e]^T @ d_out[s:e] in `dtype` (batch and K strides in elements, N contiguous) and, when d_bias is
+ * not NULL, d_bias[b] = the column sums of d_out[s:e] in fp32 (triton_jagged.py:145-240, which folds the bias reduction
+ * into the weight gradient as this does).  Every slab and row is written, zeros for an empty user.  Each sum runs in a
+ * fixed order in fp32 registers: no atomics, no workspace, bit-identical run to run.  Alignment as above. */
+int hstu_jagged_dense_bmm_wgrad(const void* jagged, int64_t jagged_row_stride, const void* d_out, int64_t d_out_row_stride,
+                                void* d_dense, int64_t d_dense_batch_stride, int64_t d_dense_k_stride, float* d_bias,
+                                int64_t d_bias_batch_stride, const void* seq_offsets, int64_t total_rows, int32_t batch, int32_t k,
+                                int32_t n, int dtype, int index_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
