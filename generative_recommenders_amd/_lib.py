@@ -97,6 +97,8 @@ SIGNATURES = {
                                          _int, _int, _vp]),
     "hstu_jagged_dense_bmm_wgrad": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _int,
                                            _int, _vp]),
+    "hstu_mips_topk_workspace_bytes": (C.c_size_t, [_i32, _i32]),
+    "hstu_mips_topk": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _int, _vp]),
     "hstu_complete_cumsum": (_int, [_vp, _vp, _i64, _int, _vp]),
     "hstu_concat_2d_jagged": (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _int, _vp]),
     "hstu_split_2d_jagged": (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _int, _vp]),

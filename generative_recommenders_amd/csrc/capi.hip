@@ -250,4 +250,30 @@ int hstu_jagged_dense_bmm_wgrad(const void* jagged, int64_t jagged_row_stride, c
                                  index_dtype, (hipStream_t)stream);
 }
 
+size_t hstu_mips_topk_workspace_bytes(int32_t batch, int32_t k) { return mips_topk_workspace_bytes(batch, k); }
+
+int hstu_mips_topk(const void* queries, int64_t q_row_stride, const void* items, int64_t item_row_stride, void* out_scores,
+                   int32_t* out_indices, void* workspace, int32_t batch, int32_t num_items, int32_t dim, int32_t k, int dtype,
+                   void* stream) {
+  const char* who = "hstu_mips_topk";
+  if (dtype != HSTU_DTYPE_BF16 && dtype != HSTU_DTYPE_F16 && dtype != HSTU_DTYPE_F32)
+    return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32 (got code %d)", who, dtype);
+  if (batch < 0) return set_error(HSTU_EINVAL, "%s: negative batch", who);
+  if (num_items <= 0 || dim <= 0) return set_error(HSTU_EINVAL, "%s: num_items and dim must be positive (got %d, %d)", who, num_items, dim);
+  const int eb = dtype == HSTU_DTYPE_F32 ? 4 : 2, epu = 16 / eb;
+  if (dim % epu) return set_error(HSTU_EINVAL, "%s: dim (%d) must be a multiple of %d elements (16 bytes); zero-pad it", who, dim, epu);
+  if (dim > kMipsTopkMaxDim) return set_error(HSTU_EINVAL, "%s: dim %d exceeds the limit of %d", who, dim, kMipsTopkMaxDim);
+  if (k < 1 || k > num_items || k > kMipsTopkMaxK)
+    return set_error(HSTU_EINVAL, "%s: k must be in [1, min(num_items, %d)] (got k = %d, num_items = %d)", who, kMipsTopkMaxK, k, num_items);
+  if (batch == 0) return HSTU_OK;
+  if (!queries || !items || !out_scores || !out_indices || !workspace)
+    return set_error(HSTU_EINVAL, "%s: queries, items, out_scores, out_indices and workspace must be non-NULL", who);
+  if (q_row_stride < dim || item_row_stride < dim) return set_error(HSTU_EINVAL, "%s: a row stride is smaller than a row", who);
+  if (!bmm_aligned(eb, queries, {q_row_stride}) || !bmm_aligned(eb, items, {item_row_stride}) || ((uintptr_t)workspace & 15) ||
+      ((uintptr_t)out_scores & (eb - 1)) || ((uintptr_t)out_indices & 3))
+    return set_error(HSTU_EINVAL, "%s: rows of queries and items and the workspace must start 16-byte aligned", who);
+  return launch_mips_topk(queries, q_row_stride, items, item_row_stride, out_scores, out_indices, workspace, batch, num_items, dim, k,
+                          dtype, (hipStream_t)stream);
+}
+
 }  // extern "C"

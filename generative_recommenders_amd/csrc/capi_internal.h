@@ -106,4 +106,11 @@ int launch_jagged_bmm_fwd(const void* jagged, int64_t a_rs, const void* dense, i
 int launch_jagged_bmm_wgrad(const void* jagged, int64_t a_rs, const void* d_out, int64_t g_rs, void* d_dense, int64_t dd_bs,
                             int64_t dd_ks, float* d_bias, int64_t db_bs, const void* offsets, int64_t total_rows, int batch,
                             int k, int n, int dtype, int index_dtype, hipStream_t st);
+
+// fused MIPS top-k (mips_topk.hip): radix select over recomputed MFMA score tiles; arguments as validated by capi.hip
+constexpr int kMipsTopkMaxK = 4096;     // the per-row sort's LDS
+constexpr int kMipsTopkMaxDim = 512;
+size_t mips_topk_workspace_bytes(int batch, int k);
+int launch_mips_topk(const void* queries, int64_t q_rs, const void* items, int64_t i_rs, void* out_scores, int32_t* out_indices,
+                     void* workspace, int batch, int num_items, int dim, int k, int dtype, hipStream_t st);
 }  // namespace hstu

@@ -499,6 +499,43 @@ def jagged_dense_bmm_wgrad(jagged: torch.Tensor, d_out: torch.Tensor, seq_offset
     return dd, db
 
 
+# ----------------------------------------------------------------------------- MIPS top-k
+def mips_topk_dim(dim: int, dtype: torch.dtype) -> int:
+    """dim rounded up to the kernel's K unit (16 bytes)"""
+    unit = _bmm_unit(dtype)
+    return -(-dim // unit) * unit
+
+
+def mips_topk(queries: torch.Tensor, items: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k items with the largest <query, item> for every query row (hstu_mips_topk): queries (B, D), items (X, D') with
+    D' >= D (columns past D are zero padding) -> (scores (B, k) in the inputs' dtype, indices (B, k) int32 into ``items``), sorted
+    by score descending, then index ascending.  No (B, X) tensor exists at any point; stream-ordered, no host sync.  Rows that
+    are not 16-byte aligned are zero-padded here (exact); a table padded once by the caller (``mips_topk_dim``) is used as is."""
+    L.require_gpu_tensor(queries, "queries")
+    L.require_gpu_tensor(items, "items")
+    if queries.dim() != 2 or items.dim() != 2 or queries.shape[1] > items.shape[1]:
+        raise RuntimeError(f"mips_topk: queries (B, D) and items (X, D) expected, got {tuple(queries.shape)} and {tuple(items.shape)}")
+    if queries.dtype not in (torch.bfloat16, torch.float16, torch.float32) or items.dtype != queries.dtype:
+        raise RuntimeError(f"mips_topk: queries and items must share a bf16 / fp16 / fp32 dtype, got {queries.dtype} and {items.dtype}")
+    if items.device != queries.device:
+        raise RuntimeError(f"mips_topk: queries are on {queries.device}, items on {items.device}")
+    B, X = queries.shape[0], items.shape[0]
+    k = int(k)
+    dp = mips_topk_dim(items.shape[1], items.dtype)
+    scores = torch.empty((B, k if k > 0 else 0), dtype=queries.dtype, device=queries.device)
+    indices = torch.empty((B, k if k > 0 else 0), dtype=torch.int32, device=queries.device)
+    lib = L.lib()
+    if B > 0 and X > 0:
+        q, t = _bmm_rows(queries, dp), _bmm_rows(items, dp)
+        ws = torch.empty(lib.hstu_mips_topk_workspace_bytes(B, max(k, 0)), dtype=torch.uint8, device=queries.device)
+        args = (q.data_ptr(), q.stride(0), t.data_ptr(), t.stride(0), scores.data_ptr(), indices.data_ptr(), ws.data_ptr())
+    else:       # nothing to launch; the library still judges the shape
+        args = (None, dp, None, dp, None, None, None)
+    with torch.cuda.device(queries.device):
+        L.check(lib.hstu_mips_topk(*args, B, X, dp, k, L.torch_dtype_code(queries.dtype), L.current_stream_ptr(queries.device)))
+    return scores, indices
+
+
 # ----------------------------------------------------------------------------- norms
 def _f32(n, device):
     return torch.empty(n, dtype=torch.float32, device=device)

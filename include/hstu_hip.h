@@ -483,6 +483,21 @@ int hstu_jagged_dense_bmm_wgrad(const void* jagged, int64_t jagged_row_stride, c
                                 int64_t d_bias_batch_stride, const void* seq_offsets, int64_t total_rows, int32_t batch, int32_t k,
                                 int32_t n, int dtype, int index_dtype, void* stream);
 
+/* ---- fused MIPS top-k: the k best items of a table per query, no (batch, num_items) score matrix ----------
+ * For every query row b: the k items x with the largest <queries[b], items[x]> (fp32 accumulation), sorted by score
+ * descending, then item index ascending; -0.0 and +0.0 are one score.  Replaces MIPSBruteForceTopK.forward
+ * (research/rails/indexing/mips_top_k.py:68-81: torch.mm + torch.topk, whose tie order is unspecified).  queries
+ * (batch, dim) and items (num_items, dim) in `dtype` with row strides in elements and unit column stride; dim a
+ * multiple of 16 bytes and at most 512, rows 16-byte aligned (zero-pad what is not).  out_scores (batch, k) contiguous
+ * in `dtype` (the fp32 score, rounded once), out_indices (batch, k) contiguous int32 positions into the table.
+ * 1 <= k <= min(num_items, 4096), num_items < 2^31.  `workspace`: hstu_mips_topk_workspace_bytes(batch, k) bytes of
+ * device memory, 16-byte aligned -- O(batch * (256 + k)), by construction independent of num_items.  A fixed launch
+ * sequence without a host sync; integer atomics only: bit-identical run to run.  batch == 0 returns without a launch. */
+size_t hstu_mips_topk_workspace_bytes(int32_t batch, int32_t k);
+int hstu_mips_topk(const void* queries, int64_t q_row_stride, const void* items, int64_t item_row_stride, void* out_scores,
+                   int32_t* out_indices, void* workspace, int32_t batch, int32_t num_items, int32_t dim, int32_t k, int dtype,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
