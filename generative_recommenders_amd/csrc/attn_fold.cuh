@@ -41,11 +41,7 @@ static int launch_bwd_quad_inst(const HstuAttnBwdParams& bp, hipStream_t st) {
   auto kern = hstu_attn_bwd_quad_kernel<T, D>;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
   if (e != hipSuccess) return set_error(HSTU_ELAUNCH, "hstu_attn_bwd: cannot reserve %d bytes of LDS: %s", smem, hipGetErrorString(e));
-  int grid = p.batch * p.heads;
-  if (QUAD_PERSIST) {
-    const int n_cu = cu_count();
-    if (grid > 2 * n_cu) grid = 2 * n_cu;
-  }
+  const int grid = p.batch * p.heads;   // one workgroup per problem
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kQuadThreads), smem, st, bp, tmax);
   return check_launch("hstu_attn_bwd(quad)");
 }

@@ -30,10 +30,6 @@
 #include <type_traits>
 #include "hstu_attn_fwd.cuh"
 
-#ifndef BIAS_ABLATE
-#define BIAS_ABLATE 0   // timing experiments only (wrong results): 1 no position histogram, 2 no time histogram, 4 bias value 0
-#endif
-
 namespace hstu {
 
 constexpr int kBwdThreads = 512;
@@ -179,7 +175,7 @@ HSTU_DEV void bwd_dq_blocks(const HstuAttnBwdParams& bp, const MaskCtx& mc, cons
           continue;
         }
         v = (col_ok && row <= rmax) ? v : 0.f;
-        if (!(BIAS_ABLATE & 16) || bp.total_rows == -12345) atomicAdd(base + min(row, rmax) * rstride + dc, v);   // (16: timing experiment, no dq adds)
+        atomicAdd(base + min(row, rmax) * rstride + dc, v);
       }
     }
   }
@@ -427,7 +423,7 @@ __global__ __launch_bounds__(kBwdThreads) void hstu_attn_bwd_kernel(const HstuAt
             const int r = 8 * h8 + j;
             const int qi = i0 + (r & 3) + 8 * (r >> 2) + 4 * hf;
             pidx[j] = bc.pos_index(qi, key);
-            xb[j] = (BIAS_ABLATE & 4) ? 0.f : bc.value(pidx[j], bkt[j]);
+            xb[j] = bc.value(pidx[j], bkt[j]);
           }
         }
         {   // two elements per VALU instruction where the ISA has a packed fp32 form (mul / add / fma)
@@ -479,14 +475,14 @@ __global__ __launch_bounds__(kBwdThreads) void hstu_attn_bwd_kernel(const HstuAt
             for (int j = 2; j >= 0; --j)
               t = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, t), 0x101, 0xf, 0xf, true)) +
                   dsv[4 * gg + j];
-            if (!(BIAS_ABLATE & 1) && t != 0.f) atomicAdd(hpos + pidx[4 * gg], t);
+            if (t != 0.f) atomicAdd(hpos + pidx[4 * gg], t);
 #pragma unroll
             for (int j = 1; j < 4; ++j)
-              if (!(BIAS_ABLATE & 1) && p16 < j && dsv[4 * gg + j] != 0.f) atomicAdd(hpos + pidx[4 * gg + j], dsv[4 * gg + j]);
+              if (p16 < j && dsv[4 * gg + j] != 0.f) atomicAdd(hpos + pidx[4 * gg + j], dsv[4 * gg + j]);
             // (collecting the pushed-out elements on lanes 0..2 with four more row shifts -- one atomic instead of three --
             // was measured: -1.4 %, and one spilled register at head dim 128)
           }
-          if (!(BIAS_ABLATE & 2) && bc.lts) {
+          if (bc.lts) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) ts_run.add(bkt[j], dsv[j]);
           }

@@ -32,10 +32,6 @@
 #ifndef FOLD_DQ32_AHEAD
 #define FOLD_DQ32_AHEAD 2  // key tiles whose fragments are requested ahead of the 32x32x16 dQ chain's MFMAs
 #endif
-#ifndef FOLD_ABLATE
-#define FOLD_ABLATE 0      // timing experiments only (WRONG results; tools/ab_bwd.py): 1 no dQ stores, 2 no dk/dv stores, 4 no stage DMA after
-#endif                     // step 0, 8 no tail, 16 no K/V DMA, 32 no dQ GEMM, 64 no pairs, 128 / 256 every problem aliases one of the first
-                           // 256 / 32 (Infinity-Cache / L2 resident data)
 // The compile-time experiments of rounds 2-5 that lost (conflict-free parks, copy-out split, L2 touch, counted vmcnt, wave priorities,
 // staggered starts, static dQ slots ...) are out of this file: docs/experiments/r05_hstu_attn_bwd_fold_with_switches.cuh.txt holds the
 // last version that carried them, docs/EXPERIMENTS.md what each measured.
@@ -131,7 +127,7 @@ HSTU_DEV void fold_pair_x(const HstuAttnParams& p, const MaskCtx& mc, const char
   // in front of the first target sees plain causal masks -- its keys are <= its rows -- and takes the plain path (two compares and the
   // lane-constant patterns instead of the general tile predicate's ~100 scalar instructions and 16 x 8 vector instructions of mask
   // bits); of a 7-tile user with <= 20 targets that is every pair but the last one or two query tiles'.
-  const bool plain = mc.simple || (HSTU_TARGETS_PLAIN && mc.has_targets && mc.win == 0 && mc.ctx == 0 && i0 + 32 <= min(len, mc.max_id));
+  const bool plain = mc.simple || (mc.has_targets && mc.win == 0 && mc.ctx == 0 && i0 + 32 <= min(len, mc.max_id));
   if (plain) mode = (k0 < i0 && i0 + 32 <= len) ? 0 : 1;    // strictly below the diagonal and all rows real
   else mode = (i0 + 32 <= len && mc.pair_fully_valid(i0, 32, k0, 32)) ? 0 : 2;
   const int key_id = mc.id_of(key);
@@ -267,7 +263,7 @@ HSTU_DEV void fold_pair_x(const HstuAttnParams& p, const MaskCtx& mc, const char
       }
       pbase = bc.pos_index(i0 + 16 * h8 + 4 * hf, key);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) xb[j] = (BIAS_ABLATE & 4) ? 0.f : bc.value(pbase - (j & 3) - 8 * (j >> 2), bkt[j]);
+      for (int j = 0; j < 8; ++j) xb[j] = bc.value(pbase - (j & 3) - 8 * (j >> 2), bkt[j]);
     }
     {   // two elements per VALU instruction where the ISA has a packed fp32 form (mul / add / fma): -1.6 % kernel time
       const f32x2 a2 = {p.alpha, p.alpha};
@@ -348,12 +344,12 @@ HSTU_DEV void fold_pair_x(const HstuAttnParams& p, const MaskCtx& mc, const char
 #pragma unroll
         for (int j = 2; j >= 0; --j)
           t = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, t), 0x101, 0xf, 0xf, true)) + dsv_[4 * gg + j];
-        if (!(BIAS_ABLATE & 1) && t != 0.f) atomicAdd(bx.hpos + pbase_ - 8 * gg, t);
+        if (t != 0.f) atomicAdd(bx.hpos + pbase_ - 8 * gg, t);
 #pragma unroll
         for (int j = 1; j < 4; ++j)
-          if (!(BIAS_ABLATE & 1) && p16 < j && dsv_[4 * gg + j] != 0.f) atomicAdd(bx.hpos + pbase_ - 8 * gg - j, dsv_[4 * gg + j]);
+          if (p16 < j && dsv_[4 * gg + j] != 0.f) atomicAdd(bx.hpos + pbase_ - 8 * gg - j, dsv_[4 * gg + j]);
       }
-      if (!(BIAS_ABLATE & 2) && bx.bc.lts) {
+      if (bx.bc.lts) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) bx.ts_run.add(bkt_[j], dsv_[j]);
       }
@@ -398,7 +394,7 @@ HSTU_DEV void fold_copy_out(const char* __restrict__ tile, char* gtile, int64_t 
     const int row = u / UPR, unit = u % UPR;
     const u32x4 v = *LDS_PTR(const u32x4, tile + tile_off<UPR>(row, unit));
     // (non-temporal: -0.2 .. -0.9 %; the same hint on the dQ stores +2.7 %: profiles/r04_fold_nt_stores.txt)
-    if (row < rows_valid && (!(FOLD_ABLATE & 2) || row_stride_bytes == -12345)) gstore16_nt(gtile + row * row_stride_bytes + unit * 16, v);
+    if (row < rows_valid) gstore16_nt(gtile + row * row_stride_bytes + unit * 16, v);
   }
 }
 
@@ -546,8 +542,7 @@ HSTU_DEV void fold_dq_slots(char* dq_head, int64_t dq_rs, const MaskCtx& mc, con
       f0 = 8 * (2 * (g & 1) + (g >> 1));
     }
     const int qrow = 32 * (sd ? bq : a) + 16 * qb + i16;
-    if (qrow < mc.len && (!(FOLD_ABLATE & 1) || dq_rs == -12345))
-      gstore16(dq_head + qrow * dq_rs + (32 * db + f0) * C::EB, u32x4{x0, x1, y0, y1});
+    if (qrow < mc.len) gstore16(dq_head + qrow * dq_rs + (32 * db + f0) * C::EB, u32x4{x0, x1, y0, y1});
   }
 }
 
@@ -570,7 +565,7 @@ HSTU_DEV void fold_dq_phase(char* dq_head, int64_t dq_rs, const MaskCtx& mc, con
 // ---- round 4: the dQ GEMM of head dim 128 as 32x32x16 chains -------------------------------------------------------------------
 // The 16x16x32 phase above gives every wave (32 features x 16 query rows) of BOTH query tiles: 8 key-tile slots per step on
 // every wave, 6 transposed reads for 2 small MFMAs per slot, one slot of read-ahead -- 2 K cycles per step of pure LDS latency
-// (removing the phase shortens the kernel by 17 %, `FOLD_ABLATE` 32).  Here wave (db = wave & 3, side = wave >> 2) owns the 32
+// (a build without the phase is 17 % shorter).  Here wave (db = wave & 3, side = wave >> 2) owns the 32
 // features of block db of ONE query tile (side 0: tile a, key tiles 0..a; side 1: tile b, key tiles 0..b): per key tile two
 // 32x32x16 MFMAs (keys 0..15, 16..31) on 8 transposed reads -- half the reads per MAC, the fragments of tile t + 2 requested
 // before the MFMAs of tile t (straight-line code per tile count).  The sides are unequal (a + 1 against b + 1 tiles) but the
@@ -659,7 +654,7 @@ HSTU_DEV void fold_dq_phase32(char* dq_head, int64_t dq_rs, const MaskCtx& mc, c
       g[jp + 1][h] = sw[1];
     }
   const int qrow = q0 + n32;
-  if (qrow < mc.len && (!(FOLD_ABLATE & 1) || dq_rs == -12345)) {
+  if (qrow < mc.len) {
     char* dst = dq_head + qrow * dq_rs + (32 * db + 8 * hf) * C::EB;
     gstore16(dst, u32x4{g[0][0], g[0][1], g[1][0], g[1][1]});
     gstore16(dst + 16 * C::EB, u32x4{g[2][0], g[2][1], g[3][0], g[3][1]});
@@ -701,8 +696,7 @@ struct FoldWork {
 
 HSTU_DEV FoldWork fold_work(const HstuAttnParams& p, int uh, int tmax) {
   FoldWork w;
-  // (FOLD_ABLATE 128 / 256: every problem aliases one of the first 256 / 32: cache-resident data)
-  w.b = user_of_slot_s(p, ((FOLD_ABLATE & 128) ? uh % 256 : (FOLD_ABLATE & 256) ? uh % 32 : uh) / p.heads);
+  w.b = user_of_slot_s(p, uh / p.heads);
   w.hd = uh % p.heads;
   w.off0 = sload_index(p.seq_offsets, w.b, p.offsets_dtype);
   w.len = min((int)(sload_index(p.seq_offsets, w.b + 1, p.offsets_dtype) - w.off0), 32 * tmax);
@@ -764,7 +758,7 @@ HSTU_DEV void fold_problem_x(const HstuAttnBwdParams& bp, kargw_t kargs, int tma
   {
     const char* kbase = (const char*)p.k + (off0 * p.k_row_stride + (int64_t)hd * p.k_head_stride) * C::EB;
     const char* vbase = (const char*)p.v + (off0 * p.v_row_stride + (int64_t)hd * p.v_head_stride) * C::EB;
-    for (int t = 0; t < ((FOLD_ABLATE & 16) ? 0 : min(nt, pre_in)); ++t) {
+    for (int t = 0; t < min(nt, pre_in); ++t) {
       char* dst = smem + t * C::PAIR;
       fold_tile_dma<T, DQK>(dst, kbase, k_rs, 32 * t, len, wave, lane, dma_fast);
       fold_tile_dma<T, DV>(dst + C::KT, vbase, v_rs, 32 * t, len, wave, lane, dma_fast);
@@ -826,7 +820,7 @@ HSTU_DEV void fold_problem_x(const HstuAttnBwdParams& bp, kargw_t kargs, int tma
     const char* st = stageA;
     if (wave <= a) { kt = wave; qt = a; }
     else if (b_on && kBwdWaves - 1 - wave <= bq) { kt = kBwdWaves - 1 - wave; qt = bq; st = stageB; }
-    if (kt >= 0 && !(FOLD_ABLATE & 64) && (mc.win == 0 || mc.pair_may_be_active(32 * qt, 32, 32 * kt, 32))) {
+    if (kt >= 0 && (mc.win == 0 || mc.pair_may_be_active(32 * qt, 32, 32 * kt, 32))) {
       const char* Kw = smem + kt * C::PAIR;
       // (the lane id is laundered per phase: LDS offsets derived from it are then recomputed where they are used --
       // a few dozen VALU instructions -- instead of being hoisted out of the step loop, where some 60 of them,
@@ -840,7 +834,7 @@ HSTU_DEV void fold_problem_x(const HstuAttnBwdParams& bp, kargw_t kargs, int tma
     HSTU_MARK(14);
     __syncthreads();   // dS' of this step published; stage reads done
     HSTU_MARK(15);
-    if (k + 1 < ns && !(FOLD_ABLATE & 4)) stage_dma(a - 1, bq + 1, bq + 1 < a - 1);
+    if (k + 1 < ns) stage_dma(a - 1, bq + 1, bq + 1 < a - 1);
     // dk / dv of the previous step's diagonal key tile (parked in K/V slot a + 1): out, by all waves
     if (k > 0) {
       const int kt1 = a + 1;
@@ -851,16 +845,14 @@ HSTU_DEV void fold_problem_x(const HstuAttnBwdParams& bp, kargw_t kargs, int tma
     // ---- phase 2: dQ of the two query tiles
     int lane2 = lane;
     asm volatile("" : "+v"(lane2));
-    if (!(FOLD_ABLATE & 32)) {
-      bool done32 = false;
-      if constexpr (DQK == 128 && DV == 128 && !BX::on) {
-        if (mc.win == 0) {       // 32x32x16 chains: needs every tile on or below the diagonal published
-          fold_dq_phase32<T, DQK>(dq_head, dq_rs, mc, smem, dsbuf, a, bq, b_on, wave, ds_scale, lane2 HSTU_TRACE_PASS);
-          done32 = true;
-        }
+    bool done32 = false;
+    if constexpr (DQK == 128 && DV == 128 && !BX::on) {
+      if (mc.win == 0) {       // 32x32x16 chains: needs every tile on or below the diagonal published
+        fold_dq_phase32<T, DQK>(dq_head, dq_rs, mc, smem, dsbuf, a, bq, b_on, wave, ds_scale, lane2 HSTU_TRACE_PASS);
+        done32 = true;
       }
-      if (!done32) fold_dq_phase<T, DQK, DV>(dq_head, dq_rs, mc, smem, dsbuf, a, bq, b_on, wave, ds_scale, lane2 HSTU_TRACE_PASS);
     }
+    if (!done32) fold_dq_phase<T, DQK, DV>(dq_head, dq_rs, mc, smem, dsbuf, a, bq, b_on, wave, ds_scale, lane2 HSTU_TRACE_PASS);
     HSTU_MARK(17);
     if (kt == wave && wave == a) {
       // diagonal step of side A: no later query tile reaches key tile `wave`, its dK/dV are final (a >= nt/2 in
@@ -878,7 +870,6 @@ HSTU_DEV void fold_problem_x(const HstuAttnBwdParams& bp, kargw_t kargs, int tma
     HSTU_MARK(23);
   }
   HSTU_MARK(20);
-  if (FOLD_ABLATE & 8) return;
   // ---- tail.  Key tiles 0..nb-1 have two partial sums: side A (wave t) and side B (wave 7 - t).  Each of the two
   // waves finishes HALF of the tile: the side-A owner hands its dV partial over and finishes dK, the side-B owner
   // hands its dK partial over and finishes dV.  Hand-over regions (fp32, lane-linear, one K/V slot's size each):

@@ -35,9 +35,6 @@ namespace hstu {
 #ifndef LONG_STAGES
 #define LONG_STAGES 3
 #endif
-#ifndef LONG_LAUNDER
-#define LONG_LAUNDER 0   // 1: lane id laundered in front of the pair (LDS offsets recomputed per pair: 214 instead of 233 registers, 3-5 % slower)
-#endif
 constexpr int kLongNW = LONG_NW;            // key tiles (owner waves) per block of the dK / dV kernel
 constexpr int kLongStages = LONG_STAGES;    // its Q / dO ring
 static_assert(kLongNW <= kBwdWaves && kLongStages >= 2 && (kLongNW + kLongStages) * 16 <= 160, "LDS");
@@ -154,11 +151,9 @@ __global__ __launch_bounds__(kBwdThreads) __attribute__((amdgpu_waves_per_eu(2, 
     if (owner && (mc.simple ? it >= kt : mc.pair_may_be_active(32 * it, 32, 32 * kt, 32))) {
       const char* Kw = smem + wave * C::PAIR;
       const char* st = ring + slot * C::PAIR;
-      // (LONG_LAUNDER: the lane id laundered, LDS offsets derived from it recomputed per pair instead of living across the loop --
-      // what the folded kernel needs next to its dQ phase; here they fit: 233 registers, 3-5 % faster)
-      int lane1 = lane;
-      if (LONG_LAUNDER) asm volatile("" : "+v"(lane1));
-      fold_pair_x<T, D, D, FoldNoBias, false, CTX>(p, mc, Kw, Kw + C::KT, st, st + C::KT, nullptr, 32 * it, 32 * kt, dk_acc, dv_acc, lane1, dmvm, nb HSTU_TRACE_PASS);
+      // (the lane id is not laundered in front of the pair, as the folded kernel needs next to its dQ phase: the LDS offsets derived
+      // from it live across the loop and fit -- 233 registers; recomputed per pair they would take 214 and run 3-5 % slower)
+      fold_pair_x<T, D, D, FoldNoBias, false, CTX>(p, mc, Kw, Kw + C::KT, st, st + C::KT, nullptr, 32 * it, 32 * kt, dk_acc, dv_acc, lane, dmvm, nb HSTU_TRACE_PASS);
     }
   }
   // ---- epilogue: every owner parks its two tiles over its own K / V tile (nobody else reads them in this kernel) and copies the
@@ -274,7 +269,7 @@ __global__ __launch_bounds__(kFwdThreads, 2) void hstu_attn_bwd_dq_kernel(const 
   };
   for (int t = 0; t < C::NS - 1 && t < ntiles; ++t) issue_tile(t, t);
   // (target rows only and every row of this wave in front of the first target: the plain causal path, as in hstu_attn_fwd_kernel)
-  const bool wave_plain = mc.simple || (HSTU_TARGETS_PLAIN && mc.has_targets && mc.win == 0 && mc.ctx == 0 && r0 + 32 <= min(len, mc.max_id));
+  const bool wave_plain = mc.simple || (mc.has_targets && mc.win == 0 && mc.ctx == 0 && r0 + 32 <= min(len, mc.max_id));
 
   for (int t = 0; t < ntiles; ++t) {
     const int slot = t % C::NS;

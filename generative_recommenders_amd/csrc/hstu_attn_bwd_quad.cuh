@@ -21,10 +21,6 @@
 #pragma once
 #include "hstu_attn_bwd_fold.cuh"
 
-#ifndef QUAD_ABLATE
-#define QUAD_ABLATE 0      // timing experiments only (WRONG results): 1 no dQ stores, 2 no dk/dv stores, 16 no K/V DMA, 32 no dQ
-#endif                     // GEMM, 64 no pairs
-
 namespace hstu {
 
 constexpr int kQuadWaves = 4;
@@ -60,7 +56,7 @@ HSTU_DEV void quad_copy_out(const char* __restrict__ tile, char* gtile, int64_t 
   for (int u = tid; u < 32 * UPR; u += kQuadThreads) {
     const int row = u / UPR, unit = u % UPR;
     const u32x4 v = *LDS_PTR(const u32x4, tile + tile_off<UPR>(row, unit));
-    if (row < rows_valid && (!(QUAD_ABLATE & 2) || row_stride_bytes == -12345)) gstore16(gtile + row * row_stride_bytes + unit * 16, v);
+    if (row < rows_valid) gstore16(gtile + row * row_stride_bytes + unit * 16, v);
   }
 }
 
@@ -111,7 +107,7 @@ HSTU_DEV void quad_dq_slots(const HstuAttnBwdParams& bp, const MaskCtx& mc, cons
   }
   // C layout of MFMA h: column i16 = query row, register r = feature 32 db + 8 g + 4 h + r
   const int qrow = 32 * qt + 16 * qb + i16;
-  if (qrow < mc.len && (!(QUAD_ABLATE & 1) || bp.total_rows == -12345)) {
+  if (qrow < mc.len) {
     char* dqrow = (char*)bp.dq + ((off0 + qrow) * bp.dq_row_stride + (int64_t)hd * bp.dq_head_stride) * C::EB;
     u32x4 v = {E::pk2(acc[0][0] * ds_scale, acc[0][1] * ds_scale), E::pk2(acc[0][2] * ds_scale, acc[0][3] * ds_scale),
                E::pk2(acc[1][0] * ds_scale, acc[1][1] * ds_scale), E::pk2(acc[1][2] * ds_scale, acc[1][3] * ds_scale)};
@@ -132,10 +128,6 @@ HSTU_DEV void quad_dq_phase(const HstuAttnBwdParams& bp, const MaskCtx& mc, cons
     default: return quad_dq_slots<T, D, 7>(bp, mc, kv, dsbuf, qt, wave, off0, hd, ds_scale, lane);
   }
 }
-
-#ifndef QUAD_PERSIST
-#define QUAD_PERSIST 0     // 1: two workgroups per CU walk the problems (grid = 2 x CUs) instead of one workgroup per problem
-#endif
 
 template <typename T, int D>
 HSTU_DEV void quad_problem(const HstuAttnBwdParams& bp, int tmax, int uh, char* smem, int tid, int lane, int wave) {
@@ -172,7 +164,7 @@ HSTU_DEV void quad_problem(const HstuAttnBwdParams& bp, int tmax, int uh, char* 
     quad_tile_dma<T, D>(stage + C::KT, dobase, do_rs, 32 * qt, len, wave, lane, dma_fast);
   };
   // ---- prologue: the whole K/V block and the first query tile, all by LDS-DMA
-  for (int t = 0; t < ((QUAD_ABLATE & 16) ? 0 : nt); ++t) {
+  for (int t = 0; t < nt; ++t) {
     char* dst = smem + t * C::PAIR;
     quad_tile_dma<T, D>(dst, kbase, k_rs, 32 * t, len, wave, lane, dma_fast);
     quad_tile_dma<T, D>(dst + C::KT, vbase, v_rs, 32 * t, len, wave, lane, dma_fast);
@@ -215,13 +207,13 @@ HSTU_DEV void quad_problem(const HstuAttnBwdParams& bp, int tmax, int uh, char* 
       else if (fin == tB) fold_park_tile<T, D>(dkB, ds_scale, smem + fin * C::PAIR, lane3);
     }
     // ---- phase 1: the pairs (i, t) of this wave's tiles
-    if (!(QUAD_ABLATE & 64) && tA <= i && (mc.win == 0 || mc.pair_may_be_active(32 * i, 32, 32 * tA, 32))) {
+    if (tA <= i && (mc.win == 0 || mc.pair_may_be_active(32 * i, 32, 32 * tA, 32))) {
       const char* Kw = smem + tA * C::PAIR;
       int lane1 = lane;
       asm volatile("" : "+v"(lane1));
       fold_pair<T, D, D>(p, mc, Kw, Kw + C::KT, stage, stage + C::KT, dsbuf + tA * Q::DSB, 32 * i, 32 * tA, dkA, dvA, lane1, dmvm HSTU_TRACE_PASS);
     }
-    if (!(QUAD_ABLATE & 64) && tB >= 0 && tB <= i && (mc.win == 0 || mc.pair_may_be_active(32 * i, 32, 32 * tB, 32))) {
+    if (tB >= 0 && tB <= i && (mc.win == 0 || mc.pair_may_be_active(32 * i, 32, 32 * tB, 32))) {
       const char* Kw = smem + tB * C::PAIR;
       int lane1 = lane;
       asm volatile("" : "+v"(lane1));
@@ -236,7 +228,7 @@ HSTU_DEV void quad_problem(const HstuAttnBwdParams& bp, int tmax, int uh, char* 
     // ---- phase 2: dQ of query tile i
     int lane2 = lane;
     asm volatile("" : "+v"(lane2));
-    if (!(QUAD_ABLATE & 32)) quad_dq_phase<T, D>(bp, mc, smem, dsbuf, i, wave, off0, hd, ds_scale, lane2);
+    quad_dq_phase<T, D>(bp, mc, smem, dsbuf, i, wave, off0, hd, ds_scale, lane2);
     // key tile i is final: V tiles are read by their owner's pairs only, and this was its last one
     {
       int lane3 = lane;
@@ -263,17 +255,7 @@ __global__ __launch_bounds__(kQuadThreads) __attribute__((amdgpu_waves_per_eu(2,
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  if (QUAD_PERSIST) {
-    const int total = bp.fwd.batch * bp.fwd.heads;
-    for (int uh = blockIdx.x; uh < total; uh += gridDim.x) {
-      int uh_l = uh;
-      asm volatile("" : "+s"(uh_l));
-      quad_problem<T, D>(bp, tmax, uh_l, smem, tid, lane, wave);
-      __syncthreads();
-    }
-  } else {
-    quad_problem<T, D>(bp, tmax, blockIdx.x, smem, tid, lane, wave);
-  }
+  quad_problem<T, D>(bp, tmax, blockIdx.x, smem, tid, lane, wave);   // one workgroup per (user, head) problem
 }
 
 }  // namespace hstu

@@ -24,9 +24,6 @@
 namespace hstu {
 
 constexpr int kFwdThreads = 256;
-#ifndef FWD_ABLATE
-#define FWD_ABLATE 0   // timing experiments only (wrong results): 1 no output stores, 2 no MFMA / element-wise work (loads and barriers only), 4 no K/V loads
-#endif
 #ifndef HSTU_FWD_MIN_WAVES
 #define HSTU_FWD_MIN_WAVES 2
 #endif
@@ -355,7 +352,7 @@ __global__ __launch_bounds__(kFwdThreads, PRECISE ? 2 : HSTU_FWD_MIN_WAVES) void
   // (target rows only -- no window, no contextual rows, no delta: DLRM-v3's call -- and every row of this wave in front of the first
   // target: the wave's masks are the plain causal ones, it takes the plain path's two compares per tile instead of the general
   // predicates' ~100 scalar instructions, and its diagonal tile the lane-constant pattern)
-  const bool wave_plain = mc.simple || (HSTU_TARGETS_PLAIN && mc.has_targets && mc.win == 0 && mc.ctx == 0 && i_shift == 0 && r0 + 32 <= min(len, mc.max_id));
+  const bool wave_plain = mc.simple || (mc.has_targets && mc.win == 0 && mc.ctx == 0 && i_shift == 0 && r0 + 32 <= min(len, mc.max_id));
   const bool diag_fast = !BIAS && wave_plain && i_shift == 0 && kv_lo == 0 && aabs > 1e-20f && aabs < 1e6f;
 
   // ---- K/V tiles stream through an NS-deep LDS ring filled by LDS-DMA: tiles t+1 .. t+NS-1 are in
@@ -379,7 +376,6 @@ __global__ __launch_bounds__(kFwdThreads, PRECISE ? 2 : HSTU_FWD_MIN_WAVES) void
     else dma_plan<T, DV, NIV>(plv, p.dv, wave, 4, lane);
   }
   auto issue_tile = [&](int t, int slot) {
-    if (FWD_ABLATE & 4) return;   // (timing experiment: no K/V loads)
     char* st = smem + slot * C::STAGE;
     if (dma_fast) {
       tile_dma_fast<NIK>(st, kbase, (uint32_t)k_rs, kv_lo + 32 * t, len, plk, wave, 4);
@@ -423,7 +419,7 @@ __global__ __launch_bounds__(kFwdThreads, PRECISE ? 2 : HSTU_FWD_MIN_WAVES) void
       tile_act = mc.pair_may_be_active(i0w, 32, j0, 32);
       tile_full = tile_act && mc.pair_fully_valid(i0w, 32, j0, 32);
     }
-    if (wave_active && tile_act && !(FWD_ABLATE & 2)) {
+    if (wave_active && tile_act) {
       const char* Kt = smem + slot * C::STAGE;
       const char* Vt = Kt + C::KT;
       // ONE accumulator chain: back-to-back dependent MFMAs forward their result, and the VALU cycles a second chain
@@ -458,9 +454,6 @@ __global__ __launch_bounds__(kFwdThreads, PRECISE ? 2 : HSTU_FWD_MIN_WAVES) void
       for (int h8 = 0; h8 < 2; ++h8) {   // two halves keep only 8 fp32 temporaries live
         float pv[8];
         if constexpr (BIAS) {
-#ifndef FWD_BIAS_ABLATE
-#define FWD_BIAS_ABLATE 0   // timing experiments only (wrong results): 1 bucket 0 for every element, 2 no table lookups
-#endif
           // two straight-line variants of the half tile (wave-uniform choice): buckets read from the user's byte matrix,
           // or computed and left there -- the bucket goes straight into its element's value, no array of 8 stays live
           char* const bslot = bcache + (2 * t + h8) * 512 + 8 * lane;
@@ -472,7 +465,7 @@ __global__ __launch_bounds__(kFwdThreads, PRECISE ? 2 : HSTU_FWD_MIN_WAVES) void
               const int key = j0 + (r & 3) + 8 * (r >> 2) + 4 * hf;
               const int bkt = (int)((w[j >> 2] >> (8 * (j & 3))) & 255u);
               float x = s[r] * p.alpha;
-              if (!(FWD_BIAS_ABLATE & 2)) x += bc.value(bc.pos_index(qi, key), bkt);
+              x += bc.value(bc.pos_index(qi, key), bkt);
               pv[j] = x * fast_sigmoid(x);
             }
           } else {
@@ -481,10 +474,10 @@ __global__ __launch_bounds__(kFwdThreads, PRECISE ? 2 : HSTU_FWD_MIN_WAVES) void
             for (int j = 0; j < 8; ++j) {
               const int r = 8 * h8 + j;
               const int key = j0 + (r & 3) + 8 * (r >> 2) + 4 * hf;
-              const int bkt = (FWD_BIAS_ABLATE & 1) ? 0 : (bc.small ? bc.bucket32(t_q32, bc.t32_at(key)) : bc.bucket(t_q1, bc.ts_at(key)));   // wave-uniform choice
+              const int bkt = bc.small ? bc.bucket32(t_q32, bc.t32_at(key)) : bc.bucket(t_q1, bc.ts_at(key));   // wave-uniform choice
               w[j >> 2] |= (unsigned)bkt << (8 * (j & 3));
               float x = s[r] * p.alpha;
-              if (!(FWD_BIAS_ABLATE & 2)) x += bc.value(bc.pos_index(qi, key), bkt);
+              x += bc.value(bc.pos_index(qi, key), bkt);
               pv[j] = x * fast_sigmoid(x);
             }
             if (head_loop) *LDS_PTR(u32x2, bslot) = w;
@@ -594,7 +587,7 @@ __global__ __launch_bounds__(kFwdThreads, PRECISE ? 2 : HSTU_FWD_MIN_WAVES) void
           const int idx = i * 64 + lane;
           const int row = idx / C::UPR_V, unit = idx % C::UPR_V;
           const u32x4 v = *LDS_PTR(const u32x4, tile + tile_off<C::UPR_V>(row, unit));
-          if (row < rows_valid && (!(FWD_ABLATE & 1) || p.batch == -12345)) gstore16_nt(obase + (int64_t)row * p.o_row_stride * C::EB + unit * 16, v);
+          if (row < rows_valid) gstore16_nt(obase + (int64_t)row * p.o_row_stride * C::EB + unit * 16, v);
         }
       }
       HSTU_MARK(21);

@@ -187,7 +187,7 @@ __global__ __launch_bounds__(kFwdThreads, HSTU_FWD_MIN_WAVES) void hstu_attn_fwd
     for (int r = 0; r < 16; ++r) oacc[d][r] = 0.f;
 
   const float aabs = fabsf(alpha);
-  const bool wave_plain = mc.simple || (HSTU_TARGETS_PLAIN && mc.has_targets && mc.win == 0 && mc.ctx == 0 && i_shift == 0 && r0 + 32 <= min(len, mc.max_id));
+  const bool wave_plain = mc.simple || (mc.has_targets && mc.win == 0 && mc.ctx == 0 && i_shift == 0 && r0 + 32 <= min(len, mc.max_id));
   const bool diag_fast = wave_plain && i_shift == 0 && kv_lo == 0 && aabs > 1e-20f && aabs < 1e6f;
 
   // ---- K/V: tile 0 converted into slot 0, tile 1 in registers

@@ -21,8 +21,8 @@
 // tile's slot is requested again, and the wave's six memory instructions of a step are spread over the chain.
 //
 // 421-445 us at 204,800 x 512 -> 2048 (layer norm + hipBLASLt: 82 + 577..607); what bounds it, and the arrangements
-// that lost (rows of the next block requested early: LNL_PRELOAD; two workgroups per CU: hstu_ln_linear2.cuh):
-// docs/EXPERIMENTS.md R4.8.
+// that lost (rows of the next block requested under the last tile of a block: 439-451 against 423-428 us, memory instructions
+// in the chain hold up the MFMAs behind them; two workgroups per CU: hstu_ln_linear2.cuh): docs/EXPERIMENTS.md R4.8.
 //
 // Work is cut into (row block, column tile) units, dealt to the persistent workgroups (one per CU) as CONTIGUOUS runs
 // of equal length: 204,800 rows = 800 blocks would leave a quarter of the chip idle in the last of 3.1 rounds; 51,200
@@ -46,24 +46,9 @@ namespace hstu {
 #ifndef LNL_AHEAD
 #define LNL_AHEAD 4        // W fragments requested ahead of the MFMA that takes them
 #endif
-#ifndef LNL_DRAIN_STORES
-#define LNL_DRAIN_STORES 0 // 1: every step waits for the previous step's stores of y as well (vmcnt(0))
-#endif
-#ifndef LNL_PRELOAD
-#define LNL_PRELOAD 0      // request the next block's rows of x under the last tile of a block (a step instantiation of its own):
-                           // measured 439-451 against 423-428 us -- memory instructions in the chain hold up the MFMAs behind them
-#endif
-#ifndef LNL_NT_STORES
-#define LNL_NT_STORES 1    // y leaves with the non-temporal hint (443 -> 421 us)
-#endif
 #ifndef LNL_X_LINES
 #define LNL_X_LINES 1      // rows of x are requested as whole 128-byte lines (8 lanes per row) and turned into MFMA fragments through
 #endif                     // the wave's LDS staging; 0: fragment-shaped loads (32 rows x 32 bytes per instruction)
-#ifndef LNL_ABLATE
-#define LNL_ABLATE 0       // experiments: 1 no stores of y, 2 no MFMA, 4 no W DMA after the prefill, 8 skip the LN arithmetic,
-                           // 16 no packing of finished tiles, 32 no bias reads, 64 no loads of x, 128 no barrier / vmcnt wait,
-                           // 256 every W request twice, 512 all stores of y land in the first MiB (cache-resident)
-#endif
 
 constexpr int kLnlK = 512;
 constexpr int kLnlWaves = 8;
@@ -115,11 +100,6 @@ HSTU_DEV void lnl_dma16(uint32_t off, const char* base, uint32_t lds_base) {
 }
 #pragma clang diagnostic pop
 
-HSTU_DEV void lnl_gstore(void* p, u32x4 v) {
-  if (LNL_NT_STORES) gstore16_nt(p, v);
-  else gstore16(p, v);
-}
-
 template <typename T> struct LnlDot;
 template <> struct LnlDot<bf16_t> {
   typedef bf16_t v2 __attribute__((ext_vector_type(2)));
@@ -152,18 +132,13 @@ HSTU_DEV const char* lnl_row_ptr(const LnLinearArgs& g, int64_t row0, int lane) 
 // LN = false: the rows as they are (the plain K = 512 product of hstu_linear_k512: no statistics, no affine)
 template <typename T, bool NORMED, bool TAB16 = false, bool LN = true>
 HSTU_DEV void lnl_load_rows(const LnLinearArgs& g, int64_t row0, const float* gam, const float* bet, int lane,
-                            u32x4 (&xf)[kLnlKS], bool preloaded, char* stage, bool x_lines = LNL_X_LINES) {
+                            u32x4 (&xf)[kLnlKS], char* stage, bool x_lines = LNL_X_LINES) {
   using DT = LnlDot<T>;
   const int m = lane & 31, h = lane >> 5;
   const int64_t row = row0 + m;
   const bool ok = row < g.rows;
   const char* xp = lnl_row_ptr(g, row0, lane);
-  if (preloaded && !x_lines) {
-    // the raw rows are already on their way: requested fragment by fragment under the last tile of the block before
-  } else if (LNL_ABLATE & 64) {
-#pragma unroll
-    for (int ks = 0; ks < kLnlKS; ++ks) asm volatile("" : "=v"(xf[ks]));
-  } else if (x_lines) {
+  if (x_lines) {
     // instruction 4 c + q fetches bytes [128 c, 128 c + 128) of the rows 8 q .. 8 q + 7 of the wave: lane L = (row 8 q + (L >> 3),
     // piece L & 7) -- eight whole lines per instruction instead of 32 quarter lines.  Each 128-byte column chunk (4 MFMA steps)
     // then crosses the wave's staging: piece p of row r sits at slot p ^ ((r >> 1) & 7) of the row (conflict-free for the
@@ -175,12 +150,10 @@ HSTU_DEV void lnl_load_rows(const LnLinearArgs& g, int64_t row0, const float* ga
       const int64_t r = row0 + 8 * q + pr;
       rp[q] = (const char*)g.x + (r < g.rows ? r : g.rows - 1) * g.ldx * 2 + 16 * pp;
     }
-    if (!preloaded) {      // (else: requested under the last tile of the block before, the same way)
 #pragma unroll
-      for (int c = 0; c < 8; ++c)
+    for (int c = 0; c < 8; ++c)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) xf[4 * c + q] = gload16(rp[q] + 128 * c);
-    }
+      for (int q = 0; q < 4; ++q) xf[4 * c + q] = gload16(rp[q] + 128 * c);
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
 #pragma unroll
@@ -195,7 +168,7 @@ HSTU_DEV void lnl_load_rows(const LnLinearArgs& g, int64_t row0, const float* ga
 #pragma unroll
     for (int ks = 0; ks < kLnlKS; ++ks) xf[ks] = gload16(xp + ks * 32);
   }
-  if (!LN || (LNL_ABLATE & 8)) return;
+  if (!LN) return;
   float s = 0.f, q = 0.f;
 #pragma unroll
   for (int ks = 0; ks < kLnlKS; ++ks)
@@ -272,7 +245,7 @@ HSTU_DEV void lnl_load_rows(const LnLinearArgs& g, int64_t row0, const float* ga
           const int r = 8 * q + pr;
           const u32x4 v = *LDS_PTR(const u32x4, stage + r * 128 + ((pp ^ ((r >> 1) & 7)) << 4));
           const int64_t gr = row0 + r;
-          if (gr < g.rows) lnl_gstore((char*)g.normed + (gr * g.ldn + 64 * c + 8 * pp) * 2, v);
+          if (gr < g.rows) gstore16_nt((char*)g.normed + (gr * g.ldn + 64 * c + 8 * pp) * 2, v);
         }
       }
     } else if (ok) {
@@ -293,10 +266,8 @@ HSTU_DEV void lnl_load_rows(const LnLinearArgs& g, int64_t row0, const float* ga
 // Piece c of row m sits at slot c ^ ((m >> 1) & 3) of its 64-byte row: conflict-free for the ds_write_b128 lane groups (8
 // consecutive rows, one piece; stores bank by 32 banks = a 128-byte window) and the ds_read_b128 groups (4 rows x 4 pieces; 64 banks).  LDS operations of one wave execute in order.
 struct LnlPacked { u32x4 lo, hi; };
-#ifndef LNL_STAGE_SHIFT
-#define LNL_STAGE_SHIFT 1    // (2: the first version's swizzle, two-way conflicts on the stores into the staging)
-#endif
-HSTU_DEV uint32_t lnl_stage_off(int m, int c) { return (uint32_t)(m * 64 + ((c ^ ((m >> LNL_STAGE_SHIFT) & 3)) << 4)); }
+// (m >> 1: the first version's swizzle, m >> 2, had two-way conflicts on the stores into the staging)
+HSTU_DEV uint32_t lnl_stage_off(int m, int c) { return (uint32_t)(m * 64 + ((c ^ ((m >> 1) & 3)) << 4)); }
 template <typename T>
 HSTU_DEV LnlPacked lnl_pack_tile(const f32x16& acc, char* stage, int lane) {
   typedef Elem<T> E;
@@ -412,12 +383,9 @@ void hstu_ln_linear_fwd_kernel(const LnLinearArgs g) {
   char* pk_dst = nullptr;
   bool ok_lo = false, ok_hi = false;     // this lane's two rows of the block exist
   int n_stores = 0;                      // store instructions of a tile that the wave really issues (none for a half without rows)
-  // (PRE: the variant for the last tile of a block that requests the next block's rows; a template parameter, not a flag --
-  // 32 conditional loads would cut every chain into basic blocks)
-  auto step = [&](f32x16& cur, f32x16& oth, bool have_prev, bool have_packed, char* row_dst, const char* xnext, auto pre) {
-    constexpr bool PRE = decltype(pre)::value;
+  auto step = [&](f32x16& cur, f32x16& oth, bool have_prev, bool have_packed, char* row_dst) {
     const int nslot = next_slot(cslot);
-    const bool do_issue = issued < nsteps && !((LNL_ABLATE & 4) && issued >= LNL_STAGES);
+    const bool do_issue = issued < nsteps;
     const char* wbase = (const char*)g.w + (int64_t)it * kLnlTileBytes;
     const uint32_t dst0 = ring0 + islot * kLnlTileBytes + 4 * wave * 1024;
     LNL_MARK(10);
@@ -425,40 +393,30 @@ void hstu_ln_linear_fwd_kernel(const LnLinearArgs g) {
     for (int ks = 0; ks < kLnlKS; ++ks) {
       Frag xb;
       xb.v = __builtin_bit_cast(typename E::vec8, xf[ks]);
-      if (!(LNL_ABLATE & 2)) cur = E::mma(wf[ks % LNL_AHEAD], xb, cur);
-      else cur[ks & 15] += (float)wf[ks % LNL_AHEAD].v[0] + (float)xb.v[0];
-      if (ks == 3 && have_packed && ok_lo) lnl_gstore(pk_dst, pk.lo);
-      if (ks == 9 && have_packed && ok_hi) lnl_gstore(pk_dst + 16 * g.ldy * 2, pk.hi);
+      cur = E::mma(wf[ks % LNL_AHEAD], xb, cur);
+      // (y leaves with the non-temporal hint: 443 -> 421 us)
+      if (ks == 3 && have_packed && ok_lo) gstore16_nt(pk_dst, pk.lo);
+      if (ks == 9 && have_packed && ok_hi) gstore16_nt(pk_dst + 16 * g.ldy * 2, pk.hi);
       if (ks == kLnlKS / 2 - 1) {
         LNL_MARK(11);
         // no lgkmcnt wait: the reads in flight are of THIS tile; the slot requested below was read by MFMAs that have issued.
         // vmcnt counts in issue order: behind the next tile's four requests there are only this step's two stores
-        // ... and, in the last tile of a block, the 15 fragments of the next block's rows requested so far
-        const int behind = (have_packed && !LNL_DRAIN_STORES ? n_stores : 0) + (PRE ? kLnlKS / 2 - 1 : 0);
-        if (LNL_ABLATE & 128) {
-        } else if (behind == 17) asm volatile("s_waitcnt vmcnt(17)\n\ts_barrier" ::: "memory");
-        else if (behind == 16) asm volatile("s_waitcnt vmcnt(16)\n\ts_barrier" ::: "memory");
-        else if (behind == 15) asm volatile("s_waitcnt vmcnt(15)\n\ts_barrier" ::: "memory");
-        else if (behind == 2) asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory");
+        const int behind = have_packed ? n_stores : 0;
+        if (behind == 2) asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory");
         else if (behind == 1) asm volatile("s_waitcnt vmcnt(1)\n\ts_barrier" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
         LNL_MARK(12);
       }
-      // fragment ks of this block's rows has had its last MFMA: its registers take the next block's row pieces now, and the
-      // load latency passes under the rest of the chain instead of in front of the next block
-      if constexpr (PRE) xf[ks] = LNL_X_LINES ? gload16(xnext + (ks & 3) * (8 * g.ldx * 2) + 128 * (ks >> 2)) : gload16(xnext + ks * 32);
       if (ks >= kLnlKS / 2 && ks % 4 == 0 && do_issue) {
         const int j = (ks - kLnlKS / 2) / 4;
         lnl_dma16(uo[j], wbase, dst0 + j * 1024);
-        if (LNL_ABLATE & 256) lnl_dma16(uo[j], wbase, dst0 + j * 1024);
       }
       wf[ks % LNL_AHEAD] = ks + LNL_AHEAD < kLnlKS ? frag_at(cslot, ks + LNL_AHEAD) : frag_at(nslot, ks + LNL_AHEAD - kLnlKS);
-      if (ks == kLnlKS / 2 + 1 && have_prev && !(LNL_ABLATE & 16)) {
+      if (ks == kLnlKS / 2 + 1 && have_prev) {
         pk = lnl_pack_tile<T>(oth, stage, lane);
         pk_dst = row_dst + (tile - 1) * 64;
-        if (LNL_ABLATE & 512) pk_dst = (char*)g.y + ((pk_dst - (char*)g.y) & 0xFFFF0) ;
       }
-      if (ks == kLnlKS / 2 + 6 && !(LNL_ABLATE & 32)) bias_into(oth, tile + 1 == g.n_tiles ? 0 : tile + 1);
+      if (ks == kLnlKS / 2 + 6) bias_into(oth, tile + 1 == g.n_tiles ? 0 : tile + 1);
 #ifdef LNL_TRACE_FINE
       if (ks % 4 == 3 && ks != kLnlKS / 2 - 1) LNL_MARK(20 + ks / 4);
 #endif
@@ -473,57 +431,39 @@ void hstu_ln_linear_fwd_kernel(const LnLinearArgs g) {
     ++tile;
   };
   auto store_packed = [&]() {
-    if (ok_lo) lnl_gstore(pk_dst, pk.lo);
-    if (ok_hi) lnl_gstore(pk_dst + 16 * g.ldy * 2, pk.hi);
+    if (ok_lo) gstore16_nt(pk_dst, pk.lo);
+    if (ok_hi) gstore16_nt(pk_dst + 16 * g.ldy * 2, pk.hi);
   };
 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   lds_barrier();      // the first tile is in the ring
   int left = nsteps;
-  bool preloaded = false;
   while (left > 0) {
     LNL_MARK(2);
-    lnl_load_rows<T, NORMED, false, LN>(g, blk * kLnlBlockRows + wave * 32, gam, bet, lane, xf, preloaded, stage);
+    lnl_load_rows<T, NORMED, false, LN>(g, blk * kLnlBlockRows + wave * 32, gam, bet, lane, xf, stage);
     LNL_MARK(3);
     const int64_t row = blk * kLnlBlockRows + wave * 32 + (lane >> 2);      // the lane's rows at store time: row, row + 16
-    const bool live = !(LNL_ABLATE & 1) || g.eps == 12345.f;
-    ok_lo = row < g.rows && live;
-    ok_hi = row + 16 < g.rows && live;
+    ok_lo = row < g.rows;
+    ok_hi = row + 16 < g.rows;
     char* row_dst = (char*)g.y + row * g.ldy * 2 + 16 * (lane & 3);
     int nt = g.n_tiles - tile;
     if (nt > left) nt = left;
     left -= nt;
-    // another block follows in this run: its rows are requested during this block's last tile
-    const char* xn = nullptr;
-    if (LNL_PRELOAD && left > 0) {
-      if (!LNL_X_LINES) xn = lnl_row_ptr(g, (blk + 1) * kLnlBlockRows + wave * 32, lane);
-      else if ((blk + 2) * kLnlBlockRows <= g.rows)      // (a last, partial block is requested when its turn comes, rows clamped)
-        xn = (const char*)g.x + ((blk + 1) * kLnlBlockRows + wave * 32 + (lane >> 3)) * g.ldx * 2 + 16 * (lane & 7);
-    }
-    preloaded = xn != nullptr;
     bias_into(acc[0], tile);
 #pragma unroll
     for (int i = 0; i < LNL_AHEAD; ++i) wf[i] = frag_at(cslot, i);
     n_stores = (__builtin_amdgcn_ballot_w64(ok_lo) != 0) + (__builtin_amdgcn_ballot_w64(ok_hi) != 0);
-    const std::false_type reg{};
-    const std::true_type pre{};
-    const int n_reg = xn ? nt - 1 : nt;     // tiles on the regular step; the block's last one requests the next block's rows
     int k = 0;
-    if (n_reg > 0) {
-      step(acc[0], acc[1], false, false, row_dst, nullptr, reg);
-      for (k = 1; k + 1 < n_reg; k += 2) {
-        step(acc[1], acc[0], true, k > 1, row_dst, nullptr, reg);
-        step(acc[0], acc[1], true, true, row_dst, nullptr, reg);
+    if (nt > 0) {
+      step(acc[0], acc[1], false, false, row_dst);
+      for (k = 1; k + 1 < nt; k += 2) {
+        step(acc[1], acc[0], true, k > 1, row_dst);
+        step(acc[0], acc[1], true, true, row_dst);
       }
-      if (k < n_reg) {
-        step(acc[1], acc[0], true, k > 1, row_dst, nullptr, reg);
+      if (k < nt) {
+        step(acc[1], acc[0], true, k > 1, row_dst);
         ++k;
       }
-    }
-    if (xn) {
-      if (k & 1) step(acc[1], acc[0], k > 0, k > 1, row_dst, xn, pre);
-      else step(acc[0], acc[1], k > 0, k > 1, row_dst, xn, pre);
-      ++k;
     }
     if (nt > 1) store_packed();
     pk = (k & 1) ? lnl_pack_tile<T>(acc[0], stage, lane) : lnl_pack_tile<T>(acc[1], stage, lane);

@@ -1,9 +1,6 @@
 // Row kernels of norm_ops.hip and their host-side launchers.  Included TWICE by norm_ops.hip, inside namespaces hstu::nw1
 // (NORM_WIDE = 1: rows of up to 1024 elements, 16-byte pieces in registers) and hstu::nw4 (NORM_WIDE = 4: up to 4096).
 
-#ifndef NORM_W5
-#define NORM_W5 1
-#endif
 #ifndef NORM_PREFETCH
 #define NORM_PREFETCH 0   // 1: u * GroupNorm(attn) requests the next row's pieces before working on the current one.  Measured with the
 #endif                    // resident grid (204800 rows of 512 bf16): forward 125 vs 122 us, backward 209 vs 202 -- no gain, off
@@ -31,7 +28,7 @@ HSTU_DEV void load_vec(RowVec<T, VEC>& r, const T* p, bool ok) {
   if constexpr (VEC == 1) {
     r.v[0] = (float)p[0];
   } else if constexpr (sizeof(T) == 2) {  // VEC == 8
-    u32x4 x = (NORM_NT & 1) ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)) : *reinterpret_cast<const u32x4*>(p);
+    u32x4 x = *reinterpret_cast<const u32x4*>(p);   // (the non-temporal hint on these loads: mixed, norm_mul bwd +6 %; profiles/r04_norm_nt.txt)
     typedef T t8 __attribute__((ext_vector_type(8)));
     t8 t = __builtin_bit_cast(t8, x);
 #pragma unroll
@@ -52,8 +49,8 @@ HSTU_DEV void store_vec(const RowVec<T, VEC>& r, T* p) {
     t8 t;
 #pragma unroll
     for (int i = 0; i < 8; ++i) t[i] = (T)r.v[i];
-    if (NORM_NT & 2) __builtin_nontemporal_store(__builtin_bit_cast(u32x4, t), reinterpret_cast<u32x4*>(p));
-    else *reinterpret_cast<u32x4*>(p) = __builtin_bit_cast(u32x4, t);
+    // (non-temporal: layer norm fwd 81 -> 68 us, SiLU fwd 81 -> 62 us, the others -1..-3 %, layer step unchanged; profiles/r04_norm_nt.txt)
+    __builtin_nontemporal_store(__builtin_bit_cast(u32x4, t), reinterpret_cast<u32x4*>(p));
   } else {
     f32x4 t = {r.v[0], r.v[1], r.v[2], r.v[3]};
     *reinterpret_cast<f32x4*>(p) = t;
@@ -85,8 +82,7 @@ HSTU_DEV float wave_sum(float x) {
 // multiply-xorshift finaliser (murmur3 fmix32) of the pair index xor a key made of both seed words and the index's high
 // word: 32-bit integer multiplies issue at a quarter of the VALU rate, and the second round the first four rounds of this
 // code carried (lowbias32) bought nothing the tests can see -- keep rate per tensor / row / column, neighbour, row and
-// seed correlations, chi-square of the uniforms (tools/dropout_hash_stats.py) -- for 2 of the pair's 5 multiplies;
-// NORM_DROP_ROUNDS=2 is the old generator (A/B builds only: the oracle restates the default).
+// seed correlations, chi-square of the uniforms (tools/dropout_hash_stats.py) -- for 2 of the pair's 5 multiplies.
 // The CPU checker of the tests restates it bit for bit (dropout_keep_mask).
 struct DropCtx {
   uint32_t thr;        // 0 = no dropout
@@ -97,21 +93,13 @@ HSTU_DEV uint32_t drop_key(uint32_t hi, uint32_t s0, uint32_t s1) {
   const uint32_t k = s1 + hi * 0x9e3779b9u;
   return s0 ^ ((k << 16) | (k >> 16));
 }
-HSTU_DEV uint32_t drop_hash(uint32_t lo, uint32_t hi, uint32_t key, uint32_t s0, uint32_t s1) {
-#if NORM_DROP_ROUNDS == 2
-  uint32_t h = lo ^ s0;
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  h ^= s1 + hi * 0x9e3779b9u;
-  h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
-  return h;
-#else
+HSTU_DEV uint32_t drop_hash(uint32_t lo, uint32_t key, uint32_t s0, uint32_t s1) {
   // (both seed words enter once more BEHIND the first multiply, as a wave-uniform addend: with the seed only XORed into the index, the masks of two
   // seeds were index-XOR permutations of one table -- mask_B[i] = mask_A[i ^ d] -- and seeds with equal keys gave equal masks;
   // one add per element pair, no multiply: round 5's advisor)
   uint32_t h = lo ^ key;
   h ^= h >> 16; h *= 0x85ebca6bu; h += s1 ^ ((s0 << 13) | (s0 >> 19)); h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
   return h;
-#endif
 }
 // v[i] *= keep(e0 + i) ? scale : 0 for i < VEC; e0 = index of v[0] in the output tensor, a multiple of VEC (rows, column
 // offsets and the output stride of a vector instantiation are multiples of VEC): the VEC / 2 pair indices of a piece then
@@ -121,7 +109,7 @@ HSTU_DEV void drop_apply(RowVec<T, VEC>& r, int64_t e0, const DropCtx& dc) {
   if constexpr (VEC == 1) {
     const uint64_t pe = (uint64_t)e0 >> 1;
     const uint32_t hi = (uint32_t)(pe >> 32);
-    const uint32_t h = drop_hash((uint32_t)pe, hi, drop_key(hi, dc.s0, dc.s1), dc.s0, dc.s1);
+    const uint32_t h = drop_hash((uint32_t)pe, drop_key(hi, dc.s0, dc.s1), dc.s0, dc.s1);
     const uint32_t r16 = (e0 & 1) ? (h >> 16) : (h & 0xffffu);
     r.v[0] = r16 >= dc.thr ? r.v[0] * dc.scale : 0.f;
   } else {
@@ -130,7 +118,7 @@ HSTU_DEV void drop_apply(RowVec<T, VEC>& r, int64_t e0, const DropCtx& dc) {
     const uint32_t key = drop_key(hi, dc.s0, dc.s1);
 #pragma unroll
     for (int j = 0; j < VEC / 2; ++j) {
-      const uint32_t h = drop_hash(lo0 + j, hi, key, dc.s0, dc.s1);
+      const uint32_t h = drop_hash(lo0 + j, key, dc.s0, dc.s1);
       r.v[2 * j] = (h & 0xffffu) >= dc.thr ? r.v[2 * j] * dc.scale : 0.f;
       r.v[2 * j + 1] = (h >> 16) >= dc.thr ? r.v[2 * j + 1] * dc.scale : 0.f;
     }
@@ -154,12 +142,9 @@ struct USrc {
   int64_t u_stride;    // elements between rows of u
   int64_t du_stride;   // ... of d u (backward)
 };
-// (NORM_FAST_SIGMOID, norm_ops.hip: the sigmoid through the hardware exp2 / rcp, 1 ulp each, as the attention kernels form it;
-// 0: expf and an IEEE divide -- ~10 more instructions per element)
-HSTU_DEV float norm_sigmoid(float x) {
-  if (NORM_FAST_SIGMOID) return fast_sigmoid(x);
-  return 1.0f / (1.0f + __expf(-x));
-}
+// (the sigmoid through the hardware exp2 / rcp, 1 ulp each, as the attention kernels form it; expf and an IEEE divide
+// take ~10 more instructions per element)
+HSTU_DEV float norm_sigmoid(float x) { return fast_sigmoid(x); }
 HSTU_DEV float silu_val(float x) {
   const float sg = norm_sigmoid(x);
   return x * sg;
@@ -668,7 +653,7 @@ __global__ __launch_bounds__(kNormThreads) void norm_mul_fwd_gn_kernel(const T* 
 // (single-chunk instance: 5 workgroups per CU asked for -- the SiLU variant sits at 98 registers, two above the 96 of a
 // fifth wave per SIMD)
 template <typename T, int VEC, int MC = max_chunks<VEC>(), bool SILU = false>
-__global__ __launch_bounds__(kNormThreads, (MC == 1 && NORM_W5 ? 5 : 1)) void norm_mul_bwd_gn_kernel(const T* dy, const T* attn, const T* u, const T* w,
+__global__ __launch_bounds__(kNormThreads, (MC == 1 ? 5 : 1)) void norm_mul_bwd_gn_kernel(const T* dy, const T* attn, const T* u, const T* w,
                                                                        const T* b, const float* mean_in,
                                                                        const float* rstd_in, T* dattn, T* du,
                                                                        float* partial, int64_t rows, int heads, int hdim,
