@@ -276,4 +276,83 @@ int hstu_mips_topk(const void* queries, int64_t q_row_stride, const void* items,
                           dtype, (hipStream_t)stream);
 }
 
+// ---- multitask prediction head --------------------------------------------------------------------------------------------
+static int validate_multitask(const char* who, const void* x, int64_t x_rs, const void* dx, int64_t dx_rs, const void* ln_w,
+                              const void* ln_b, int64_t rows, int32_t dim, int32_t tasks, int32_t nbin, int dtype,
+                              std::initializer_list<const void*> f32_ptrs, const void* workspace, bool* vec) {
+  if (dtype != HSTU_DTYPE_BF16 && dtype != HSTU_DTYPE_F16 && dtype != HSTU_DTYPE_F32)
+    return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32 (got code %d)", who, dtype);
+  if (tasks < 1 || tasks > HSTU_MULTITASK_MAX_TASKS)
+    return set_error(HSTU_EINVAL, "%s: num_tasks must be in [1, %d] (got %d)", who, HSTU_MULTITASK_MAX_TASKS, tasks);
+  if (nbin < 0 || nbin > tasks)
+    return set_error(HSTU_EINVAL, "%s: num_binary must be in [0, num_tasks = %d] (got %d)", who, tasks, nbin);
+  if (rows < 0) return set_error(HSTU_EINVAL, "%s: negative rows", who);
+  if (dim <= 0) return set_error(HSTU_EINVAL, "%s: dim must be positive (got %d)", who, dim);
+  const int eb = dtype == HSTU_DTYPE_F32 ? 4 : 2, epu = 16 / eb;
+  const uintptr_t bits = (uintptr_t)x | (uintptr_t)dx | (uintptr_t)ln_w | (uintptr_t)ln_b;
+  if (bits & (eb - 1)) return set_error(HSTU_EINVAL, "%s: x, dx and the norm's weight and bias must be aligned to their element size (%d bytes)", who, eb);
+  for (const void* p : f32_ptrs)
+    if ((uintptr_t)p & 3) return set_error(HSTU_EINVAL, "%s: an fp32 tensor is not 4-byte aligned", who);
+  if ((uintptr_t)workspace & 15) return set_error(HSTU_EINVAL, "%s: the workspace must be 16-byte aligned", who);
+  if (x_rs < dim || (dx && dx_rs < dim)) return set_error(HSTU_EINVAL, "%s: a row stride is smaller than a row", who);
+  *vec = dim % epu == 0 && (bits & 15) == 0 && (x_rs * eb) % 16 == 0 && (!dx || (dx_rs * eb) % 16 == 0);
+  const int lim = *vec ? kMultitaskMaxDimVec : kMultitaskMaxDimScalar;
+  if (dim > lim) return set_error(HSTU_EINVAL, "%s: dim %d exceeds the %d supported with this alignment", who, dim, lim);
+  return HSTU_OK;
+}
+
+size_t hstu_multitask_head_workspace_bytes(int32_t dim, int32_t num_tasks) { return multitask_head_workspace_bytes(dim, num_tasks); }
+
+int hstu_multitask_head_fwd(const void* x, int64_t x_row_stride, const void* ln_weight, const void* ln_bias, float eps,
+                            const float* w, const float* c, const float* labels, const float* weights, float* logits,
+                            float* preds, float* mean, float* rstd, float* loss, float* weight_sum, void* workspace,
+                            int64_t rows, int32_t dim, int32_t num_tasks, int32_t num_binary, float loss_scale, int dtype,
+                            void* stream) {
+  const char* who = "hstu_multitask_head_fwd";
+  bool vec = false;
+  if (int e = validate_multitask(who, x, x_row_stride, nullptr, 0, ln_weight, ln_bias, rows, dim, num_tasks, num_binary, dtype,
+                                 {w, c, labels, weights, logits, preds, mean, rstd, loss, weight_sum}, workspace, &vec))
+    return e;
+  if (rows == 0) {   // (a (T, 0) labels tensor has no address: the reduced outputs are zeroed wherever they are given)
+    if (loss) (void)hipMemsetAsync(loss, 0, num_tasks * sizeof(float), (hipStream_t)stream);
+    if (weight_sum) (void)hipMemsetAsync(weight_sum, 0, num_tasks * sizeof(float), (hipStream_t)stream);
+    return HSTU_OK;
+  }
+  if (labels && (!loss || !weight_sum)) return set_error(HSTU_EINVAL, "%s: labels need loss and weight_sum", who);
+  if (weights && !labels) return set_error(HSTU_EINVAL, "%s: weights without labels", who);
+  if (!x || !ln_weight || !ln_bias || !w || !c || !preds || (labels && !workspace))
+    return set_error(HSTU_EINVAL, "%s: x, ln_weight, ln_bias, w, c, preds (and with labels the workspace) must be non-NULL", who);
+  return launch_multitask_head_fwd(x, x_row_stride, ln_weight, ln_bias, eps, w, c, labels, weights, logits, preds, mean, rstd, loss,
+                                   weight_sum, workspace, rows, dim, num_tasks, num_binary, loss_scale, dtype, vec, (hipStream_t)stream);
+}
+
+int hstu_multitask_head_bwd(const float* grad_loss, const float* grad_pred, const void* x, int64_t x_row_stride,
+                            const void* ln_weight, const void* ln_bias, const float* w, const float* labels, const float* weights,
+                            const float* logits, const float* mean, const float* rstd, const float* weight_sum, void* dx,
+                            int64_t dx_row_stride, float* dw, float* dc, float* dln_weight, float* dln_bias, void* workspace,
+                            int64_t rows, int32_t dim, int32_t num_tasks, int32_t num_binary, float loss_scale, int dtype,
+                            void* stream) {
+  const char* who = "hstu_multitask_head_bwd";
+  bool vec = false;
+  if (int e = validate_multitask(who, x, x_row_stride, dx, dx_row_stride, ln_weight, ln_bias, rows, dim, num_tasks, num_binary, dtype,
+                                 {grad_loss, grad_pred, w, labels, weights, logits, mean, rstd, weight_sum, dw, dc, dln_weight, dln_bias},
+                                 workspace, &vec))
+    return e;
+  if (!dw || !dc || !dln_weight || !dln_bias) return set_error(HSTU_EINVAL, "%s: dw, dc, dln_weight and dln_bias are required", who);
+  if (rows == 0) {
+    hipStream_t st = (hipStream_t)stream;
+    (void)hipMemsetAsync(dw, 0, (size_t)num_tasks * dim * sizeof(float), st);
+    (void)hipMemsetAsync(dc, 0, num_tasks * sizeof(float), st);
+    (void)hipMemsetAsync(dln_weight, 0, dim * sizeof(float), st);
+    (void)hipMemsetAsync(dln_bias, 0, dim * sizeof(float), st);
+    return HSTU_OK;
+  }
+  if (grad_loss && (!labels || !weight_sum)) return set_error(HSTU_EINVAL, "%s: grad_loss needs labels and weight_sum", who);
+  if (!x || !ln_weight || !ln_bias || !w || !logits || !mean || !rstd || !dx || !workspace)
+    return set_error(HSTU_EINVAL, "%s: x, ln_weight, ln_bias, w, logits, mean, rstd, dx and the workspace must be non-NULL", who);
+  return launch_multitask_head_bwd(grad_loss, grad_pred, x, x_row_stride, ln_weight, ln_bias, w, labels, weights, logits, mean, rstd,
+                                   weight_sum, dx, dx_row_stride, dw, dc, dln_weight, dln_bias, workspace, rows, dim, num_tasks,
+                                   num_binary, loss_scale, dtype, vec, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -113,4 +113,20 @@ constexpr int kMipsTopkMaxDim = 512;
 size_t mips_topk_workspace_bytes(int batch, int k);
 int launch_mips_topk(const void* queries, int64_t q_rs, const void* items, int64_t i_rs, void* out_scores, int32_t* out_indices,
                      void* workspace, int batch, int num_items, int dim, int k, int dtype, hipStream_t st);
+
+// multitask prediction head (multitask_ops.hip): SwishLayerNorm + task projection + predictions + task losses per row, and
+// the backward; arguments as validated by capi.hip.  `vec`: rows are read as 16-byte pieces (dim, pointers and row strides
+// allow it), else element by element -- the two dim limits are those of hstu_swish_layer_norm_fwd
+constexpr int kMultitaskMaxDimVec = 4096;
+constexpr int kMultitaskMaxDimScalar = 2048;
+size_t multitask_head_workspace_bytes(int dim, int tasks);
+int launch_multitask_head_fwd(const void* x, int64_t x_rs, const void* ln_w, const void* ln_b, float eps, const float* w,
+                              const float* c, const float* labels, const float* weights, float* logits, float* preds,
+                              float* mean, float* rstd, float* loss, float* weight_sum, void* workspace, int64_t rows, int dim,
+                              int tasks, int nbin, float loss_scale, int dtype, bool vec, hipStream_t st);
+int launch_multitask_head_bwd(const float* grad_loss, const float* grad_pred, const void* x, int64_t x_rs, const void* ln_w,
+                              const void* ln_b, const float* w, const float* labels, const float* weights, const float* logits,
+                              const float* mean, const float* rstd, const float* weight_sum, void* dx, int64_t dx_rs, float* dw,
+                              float* dc, float* dln_w, float* dln_b, void* workspace, int64_t rows, int dim, int tasks, int nbin,
+                              float loss_scale, int dtype, bool vec, hipStream_t st);
 }  // namespace hstu

@@ -907,3 +907,81 @@ def sampled_softmax_bwd(g_row, lse, q, pos_emb, pos_ids, neg_rows, neg_ids, tabl
             dpos.data_ptr(), dpos.stride(0), dtable.data_ptr(), L.torch_dtype_code(q.dtype), L.current_stream_ptr(q.device)))
     return dq, dpos, dtable
 
+
+
+# ---- multitask prediction head (hstu_multitask_head_fwd / _bwd) --------------------------------------------------------
+MULTITASK_MAX_TASKS = 8          # HSTU_MULTITASK_MAX_TASKS
+MULTITASK_MAX_BLOCKS = 1024      # HSTU_MULTITASK_MAX_BLOCKS: grid cap of the row kernels
+MULTITASK_ROWS_PER_BLOCK = 4     # HSTU_MULTITASK_ROWS_PER_BLOCK: one row per wavefront
+
+
+def _rows_2d(x: torch.Tensor) -> torch.Tensor:
+    """(rows, dim) with unit column stride; a column slice of a wider buffer is passed as it is (row stride)"""
+    return x if x.stride(1) == 1 and x.stride(0) >= x.shape[1] else x.contiguous()
+
+
+def multitask_head_supported(x: torch.Tensor, num_tasks: int) -> bool:
+    """whether the fused head takes (rows, dim) activations and num_tasks tasks: the dim limits of swish_layer_norm"""
+    if not (x.is_cuda and x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16, torch.float32)):
+        return False
+    if not 1 <= num_tasks <= MULTITASK_MAX_TASKS or x.shape[1] < 1:
+        return False
+    es = x.element_size()
+    xr = x if x.stride(1) == 1 and x.stride(0) >= x.shape[1] else None
+    vec = x.shape[1] % (16 // es) == 0 and (xr is None or (xr.data_ptr() % 16 == 0 and (xr.stride(0) * es) % 16 == 0))
+    return x.shape[1] <= (4096 if vec else 2048)
+
+
+def _f32c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return None if t is None else t.to(torch.float32).contiguous()
+
+
+def multitask_head_fwd(x, ln_weight, ln_bias, eps, weight, bias, labels, weights, num_binary_tasks, loss_scale):
+    """Returns (logits, preds, mean, rstd, loss, weight_sum): logits / preds (T, rows) fp32, loss / weight_sum (T) fp32 or
+    None without labels (the inference form)."""
+    L.require_gpu_tensor(x, "x")
+    x = _rows_2d(x)
+    rows, dim = x.shape
+    tasks = weight.shape[0]
+    dev = x.device
+    g, b = ln_weight.to(x.dtype).contiguous(), ln_bias.to(x.dtype).contiguous()
+    w, c = _f32c(weight), _f32c(bias)
+    labels, weights = _f32c(labels), _f32c(weights)
+    logits = torch.empty((tasks, rows), dtype=torch.float32, device=dev)
+    preds = torch.empty((tasks, rows), dtype=torch.float32, device=dev)
+    mean, rstd = _f32(rows, dev), _f32(rows, dev)
+    loss = wsum = ws = None
+    if labels is not None:
+        loss, wsum = _f32(tasks, dev), _f32(tasks, dev)
+        ws = torch.empty(L.lib().hstu_multitask_head_workspace_bytes(dim, tasks), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().hstu_multitask_head_fwd(x.data_ptr(), x.stride(0), g.data_ptr(), b.data_ptr(), float(eps), w.data_ptr(),
+                                                c.data_ptr(), _vp(labels), _vp(weights), logits.data_ptr(), preds.data_ptr(),
+                                                mean.data_ptr(), rstd.data_ptr(), _vp(loss), _vp(wsum), _vp(ws), rows, dim, tasks,
+                                                int(num_binary_tasks), float(loss_scale), L.torch_dtype_code(x.dtype),
+                                                L.current_stream_ptr(dev)))
+    return logits, preds, mean, rstd, loss, wsum
+
+
+def multitask_head_bwd(grad_loss, grad_pred, x, ln_weight, ln_bias, weight, labels, weights, logits, mean, rstd, weight_sum,
+                       num_binary_tasks, loss_scale):
+    """dx (x's dtype), dweight (T, dim), dbias (T), dln_weight, dln_bias (dim), the last four fp32"""
+    x = _rows_2d(x)
+    rows, dim = x.shape
+    tasks = weight.shape[0]
+    dev = x.device
+    g, b = ln_weight.to(x.dtype).contiguous(), ln_bias.to(x.dtype).contiguous()
+    w = _f32c(weight)
+    labels, weights, grad_loss, grad_pred = _f32c(labels), _f32c(weights), _f32c(grad_loss), _f32c(grad_pred)
+    dx = torch.empty((rows, dim), dtype=x.dtype, device=dev)
+    dw = torch.empty((tasks, dim), dtype=torch.float32, device=dev)
+    dc, dg, db = _f32(tasks, dev), _f32(dim, dev), _f32(dim, dev)
+    ws = torch.empty(L.lib().hstu_multitask_head_workspace_bytes(dim, tasks), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().hstu_multitask_head_bwd(_vp(grad_loss), _vp(grad_pred), x.data_ptr(), x.stride(0), g.data_ptr(), b.data_ptr(),
+                                                w.data_ptr(), _vp(labels), _vp(weights), logits.data_ptr(), mean.data_ptr(),
+                                                rstd.data_ptr(), _vp(weight_sum), dx.data_ptr(), dx.stride(0), dw.data_ptr(),
+                                                dc.data_ptr(), dg.data_ptr(), db.data_ptr(), ws.data_ptr(), rows, dim, tasks,
+                                                int(num_binary_tasks), float(loss_scale), L.torch_dtype_code(x.dtype),
+                                                L.current_stream_ptr(dev)))
+    return dx, dw, dc, dg, db

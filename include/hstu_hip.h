@@ -498,6 +498,45 @@ int hstu_mips_topk(const void* queries, int64_t q_row_stride, const void* items,
                    int32_t* out_indices, void* workspace, int32_t batch, int32_t num_items, int32_t dim, int32_t k, int dtype,
                    void* stream);
 
+/* ---- multitask prediction head: SwishLayerNorm + task projection + predictions + task losses in one row pass ----
+ * Per row l of x (rows, dim; `dtype`, row stride in elements, unit column stride), fp32 math throughout:
+ *   y = x * sigmoid(LayerNorm(x) ln_weight + ln_bias)                  (never written to memory)
+ *   logits[t, l] = <y, w[t]> + c[t]                                    w (num_tasks, dim), c (num_tasks): fp32
+ *   preds[t, l]  = sigmoid(logits[t, l]) for t < num_binary (the binary tasks come first), logits[t, l] otherwise
+ *   loss[t] = sum_l weights[t, l] * (max(z, 0) - z label + log1p(exp(-|z|)) | (z - label)^2)
+ *             / max(weight_sum[t], 1) * loss_scale,   weight_sum[t] = sum_l weights[t, l]
+ * Replaces everything behind the first projection of DefaultMultitaskModule (modules/multitask_module.py:70-104 predictions,
+ * :107-133 labels and weights, :136-191 losses, :233-277 forward) with the prediction module of modules/dlrm_hstu.py:139-149
+ * (Linear -> SwishLayerNorm -> Linear): ops/layer_norm.py:79-112 + torch.nn.Linear + the (T, L) torch ops.
+ * logits, preds, labels, weights: (num_tasks, rows) fp32 contiguous; mean, rstd (rows) fp32 (outputs of the forward, may be
+ * NULL; inputs of the backward); loss, weight_sum (num_tasks) fp32.  ln_weight / ln_bias in `dtype`, as
+ * hstu_swish_layer_norm_fwd takes them, and with its dim limits (4096 for rows of 16-byte pieces, 2048 otherwise).
+ * weights == NULL: all ones.  labels == NULL (inference): only logits (may be NULL), preds, mean, rstd are written.
+ * Sums over rows run in a fixed order (per-workgroup partials in `workspace`, then a finish kernel): no float atomics,
+ * bit-identical run to run.  `workspace`: hstu_multitask_head_workspace_bytes(dim, num_tasks) bytes of device memory,
+ * 16-byte aligned, independent of rows.  rows == 0 zeroes loss / weight_sum and launches nothing. */
+#define HSTU_MULTITASK_MAX_TASKS 8
+#define HSTU_MULTITASK_MAX_BLOCKS 1024      /* grid cap of the row kernels (they loop over rows beyond it) ... */
+#define HSTU_MULTITASK_ROWS_PER_BLOCK 4     /* ... and the rows a workgroup works on at once (one per wavefront) */
+size_t hstu_multitask_head_workspace_bytes(int32_t dim, int32_t num_tasks);
+int hstu_multitask_head_fwd(const void* x, int64_t x_row_stride, const void* ln_weight, const void* ln_bias, float eps,
+                            const float* w, const float* c, const float* labels, const float* weights, float* logits,
+                            float* preds, float* mean, float* rstd, float* loss, float* weight_sum, void* workspace,
+                            int64_t rows, int32_t dim, int32_t num_tasks, int32_t num_binary, float loss_scale, int dtype,
+                            void* stream);
+/* Gradients of sum_t grad_loss[t] loss[t] + sum_{t,l} grad_pred[t, l] preds[t, l] (either may be NULL):
+ *   d logits[t, l] = grad_loss[t] loss_scale weights[t, l] / max(weight_sum[t], 1) * (sigmoid(z) - label | 2 (z - label))
+ *                    + grad_pred[t, l] * (p (1 - p) | 1)
+ * then y is recomputed, d y = sum_t d logits[t] w[t] goes through the SwishLayerNorm backward into dx (`dtype`, row
+ * stride in elements), and dw (num_tasks, dim), dc (num_tasks), dln_weight, dln_bias (dim) are accumulated in fp32 in a
+ * fixed order.  logits / mean / rstd / weight_sum as the forward wrote them.  rows == 0 zeroes the four reduced outputs. */
+int hstu_multitask_head_bwd(const float* grad_loss, const float* grad_pred, const void* x, int64_t x_row_stride,
+                            const void* ln_weight, const void* ln_bias, const float* w, const float* labels, const float* weights,
+                            const float* logits, const float* mean, const float* rstd, const float* weight_sum, void* dx,
+                            int64_t dx_row_stride, float* dw, float* dc, float* dln_weight, float* dln_bias, void* workspace,
+                            int64_t rows, int32_t dim, int32_t num_tasks, int32_t num_binary, float loss_scale, int dtype,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
