@@ -147,6 +147,15 @@ SIGNATURES = {
                                        _i32, _i32, _f32, _int, _vp]),
     "hstu_multitask_head_bwd": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                                        _vp, _i64, _i32, _i32, _i32, _f32, _int, _vp]),
+    "hstu_action_encode_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _i32, _int,
+                                      _int, _vp]),
+    "hstu_action_encode_bwd_workspace_bytes": (C.c_size_t, [_i64, _i32]),
+    "hstu_action_encode_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i64, _i32, _i32,
+                                      _int, _int, _vp]),
+    "hstu_combine_embeddings_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _int, _int,
+                                           _int, _vp]),
+    "hstu_combine_embeddings_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _int, _int, _int,
+                                           _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -985,3 +985,169 @@ def multitask_head_bwd(grad_loss, grad_pred, x, ln_weight, ln_bias, weight, labe
                                                 int(num_binary_tasks), float(loss_scale), L.torch_dtype_code(x.dtype),
                                                 L.current_stream_ptr(dev)))
     return dx, dw, dc, dg, db
+
+
+# ---- input preprocessors (hstu_action_encode_* / hstu_combine_embeddings_*) ------------------------------------------
+ACTION_ENCODE_MAX_TYPES = 64     # HSTU_ACTION_ENCODE_MAX_TYPES
+COMBINE_SUM, COMBINE_INTERLEAVE_ALL, COMBINE_INTERLEAVE_UIH = 0, 1, 2     # HSTU_COMBINE_*
+MAX_ROWS = 2**31 - 1
+
+
+def _host_i64(values):
+    """a host int64 array that travels as kernel arguments (kept alive by the caller for the duration of the call)"""
+    values = [int(v) for v in values]
+    return (C.c_int64 * max(len(values), 1))(*values)
+
+
+def _i64_rows(t: Optional[torch.Tensor], name: str, rows: int) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    L.require_gpu_tensor(t, name)
+    if t.dtype != torch.int64:
+        raise RuntimeError(f"{name} must be int64, got {t.dtype}")
+    if t.numel() != rows:
+        raise RuntimeError(f"{name} has {t.numel()} values, {rows} expected")
+    return t.contiguous().view(-1)
+
+
+def _offset_pair(a: torch.Tensor, b: torch.Tensor, what: str):
+    """two offset / count vectors in ONE integer type (that of the first)"""
+    a = _idx(a)
+    b = _idx(b)
+    if b.dtype != a.dtype:
+        b = b.to(a.dtype)
+    if a.device != b.device:
+        raise RuntimeError(f"{what}: the offset tensors live on different devices")
+    return a, b
+
+
+def _check_action_args(weights, thresholds, total_uih_len, total_targets) -> None:
+    if not 1 <= len(weights) <= ACTION_ENCODE_MAX_TYPES:
+        raise RuntimeError(f"action_encode: 1..{ACTION_ENCODE_MAX_TYPES} action types, got {len(weights)}")
+    if total_uih_len < 0 or total_targets < 0 or total_uih_len + total_targets > MAX_ROWS:
+        raise RuntimeError(f"action_encode: {total_uih_len} + {total_targets} rows: 0 .. 2^31 - 1 are supported")
+    if len(thresholds) > len(weights):
+        raise RuntimeError("action_encode: more watchtime thresholds than action types")
+
+
+def action_encode_fwd(actions, watchtimes, uih_offsets, target_offsets, table, target_table, weights, thresholds,
+                      total_uih_len: int, total_targets: int, dtype: torch.dtype) -> torch.Tensor:
+    """(total_uih_len + total_targets, T * Da) in `dtype`.  weights: the T combined action weights (python ints);
+    thresholds: [(threshold, weight)] of the watchtime rule."""
+    L.require_gpu_tensor(table, "table")
+    _check_action_args(weights, thresholds, total_uih_len, total_targets)
+    T, da = table.shape
+    if T != len(weights) or target_table.numel() != T * da:
+        raise RuntimeError(f"action_encode: table {tuple(table.shape)}, target_table {tuple(target_table.shape)} and "
+                           f"{len(weights)} weights do not fit together")
+    dev = table.device
+    actions = _i64_rows(actions, "actions", total_uih_len)
+    watchtimes = _i64_rows(watchtimes, "watchtimes", total_uih_len) if thresholds else None
+    uo, to = _offset_pair(uih_offsets, target_offsets, "action_encode")
+    L.require_gpu_tensor(uo, "uih_offsets")
+    tab, ttab = _f32c(table), _f32c(target_table)
+    out = torch.empty((total_uih_len + total_targets, T * da), dtype=dtype, device=dev)
+    w, th, tw = _host_i64(weights), _host_i64([t for t, _ in thresholds]), _host_i64([x for _, x in thresholds])
+    with torch.cuda.device(dev):
+        L.check(L.lib().hstu_action_encode_fwd(_vp(actions), _vp(watchtimes), uo.data_ptr(), to.data_ptr(), tab.data_ptr(),
+                                               ttab.data_ptr(), w, T, th, tw, len(thresholds), out.data_ptr(), total_uih_len,
+                                               total_targets, uo.numel() - 1, da, L.torch_dtype_code(dtype),
+                                               L.index_dtype_code(uo), L.current_stream_ptr(dev)))
+    return out
+
+
+def action_encode_bwd(d_out, actions, watchtimes, uih_offsets, target_offsets, weights, thresholds, total_uih_len: int,
+                      total_targets: int, embedding_dim: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """d_table (T, Da) and d_target_table (1, T * Da), fp32, summed in a fixed order"""
+    L.require_gpu_tensor(d_out, "d_out")
+    T, da, dev = len(weights), int(embedding_dim), d_out.device
+    d_out = d_out.contiguous()
+    actions = _i64_rows(actions, "actions", total_uih_len)
+    watchtimes = _i64_rows(watchtimes, "watchtimes", total_uih_len) if thresholds else None
+    uo, to = _offset_pair(uih_offsets, target_offsets, "action_encode")
+    d_table = torch.empty((T, da), dtype=torch.float32, device=dev)
+    d_target = torch.empty((1, T * da), dtype=torch.float32, device=dev)
+    ws = torch.empty(L.lib().hstu_action_encode_bwd_workspace_bytes(total_uih_len + total_targets, T * da), dtype=torch.uint8,
+                     device=dev)
+    w, th, tw = _host_i64(weights), _host_i64([t for t, _ in thresholds]), _host_i64([x for _, x in thresholds])
+    with torch.cuda.device(dev):
+        L.check(L.lib().hstu_action_encode_bwd(d_out.data_ptr(), _vp(actions), _vp(watchtimes), uo.data_ptr(), to.data_ptr(), w, T,
+                                               th, tw, len(thresholds), d_table.data_ptr(), d_target.data_ptr(), ws.data_ptr(),
+                                               total_uih_len, total_targets, uo.numel() - 1, da,
+                                               L.torch_dtype_code(d_out.dtype), L.index_dtype_code(uo),
+                                               L.current_stream_ptr(dev)))
+    return d_table, d_target
+
+
+def combine_out_rows(mode: int, total_uih_len: int, total_targets: int, batch: int, contextual_len: int) -> int:
+    """the number of output rows, from the integers the caller already holds (no device read)"""
+    seq = {COMBINE_SUM: total_uih_len + total_targets, COMBINE_INTERLEAVE_ALL: 2 * (total_uih_len + total_targets),
+           COMBINE_INTERLEAVE_UIH: 2 * total_uih_len + total_targets}
+    if mode not in seq:
+        raise RuntimeError(f"combine_embeddings: unknown mode {mode}")
+    return batch * contextual_len + seq[mode]
+
+
+def _check_combine(total_uih_len, total_targets, out_rows):
+    if total_uih_len < 0 or total_targets < 0 or out_rows > MAX_ROWS:
+        raise RuntimeError(f"combine_embeddings: {total_uih_len} + {total_targets} rows in, {out_rows} out: 0 .. 2^31 - 1 "
+                           "are supported")
+
+
+def combine_embeddings_fwd(content, action, contextual, timestamps, seq_offsets, num_targets, out_offsets, mode: int,
+                           total_uih_len: int, total_targets: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(out rows, D) embeddings and (out rows) int64 timestamps; contextual (B, C, D) or None, action (rows, D) or None"""
+    L.require_gpu_tensor(content, "content_embeddings")
+    L.require_gpu_tensor(timestamps, "seq_timestamps")
+    if timestamps.dtype != torch.int64:
+        raise RuntimeError(f"seq_timestamps must be int64, got {timestamps.dtype}")
+    for name, t in (("action_embeddings", action), ("contextual_embeddings", contextual)):
+        if t is not None and (t.dtype != content.dtype or t.device != content.device):
+            raise RuntimeError(f"{name} is {t.dtype} on {t.device}, content_embeddings {content.dtype} on {content.device}")
+    total, D = content.shape
+    batch = seq_offsets.numel() - 1
+    C_len = 0 if contextual is None else contextual.shape[1]
+    out_rows = combine_out_rows(mode, total_uih_len, total_targets, batch, C_len)
+    _check_combine(total_uih_len, total_targets, out_rows)
+    if total != total_uih_len + total_targets or timestamps.numel() != total or (action is not None and action.shape != content.shape):
+        raise RuntimeError(f"combine_embeddings: content {tuple(content.shape)}, {timestamps.numel()} timestamps and "
+                           f"total_uih_len + total_targets = {total_uih_len + total_targets} do not fit together")
+    if contextual is not None and tuple(contextual.shape) != (batch, C_len, D):
+        raise RuntimeError(f"contextual_embeddings must be (B, C, D) = ({batch}, {C_len}, {D}), got {tuple(contextual.shape)}")
+    so, oo = _offset_pair(seq_offsets, out_offsets, "combine_embeddings")
+    nt = None if num_targets is None else _offset_pair(so, num_targets, "combine_embeddings")[1]
+    content, timestamps = content.contiguous(), timestamps.contiguous()
+    action = None if action is None else action.contiguous()
+    contextual = None if contextual is None else contextual.contiguous()
+    dev = content.device
+    out = torch.empty((out_rows, D), dtype=content.dtype, device=dev)
+    out_ts = torch.empty((out_rows,), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().hstu_combine_embeddings_fwd(content.data_ptr(), _vp(action), _vp(contextual), timestamps.data_ptr(),
+                                                    so.data_ptr(), _vp(nt), oo.data_ptr(), out.data_ptr(), out_ts.data_ptr(),
+                                                    total_uih_len, total_targets, batch, C_len, D, mode,
+                                                    L.torch_dtype_code(content.dtype), L.index_dtype_code(so),
+                                                    L.current_stream_ptr(dev)))
+    return out, out_ts
+
+
+def combine_embeddings_bwd(d_out, seq_offsets, num_targets, out_offsets, mode: int, total_uih_len: int, total_targets: int,
+                           contextual_len: int, want_action: bool):
+    """(d_content, d_action or None, d_contextual (B, C, D) or None) in d_out's dtype: every row read from the output row
+    that copied it"""
+    L.require_gpu_tensor(d_out, "d_out")
+    d_out = d_out.contiguous()
+    D, dev = d_out.shape[1], d_out.device
+    batch = seq_offsets.numel() - 1
+    total = total_uih_len + total_targets
+    so, oo = _offset_pair(seq_offsets, out_offsets, "combine_embeddings")
+    nt = None if num_targets is None else _offset_pair(so, num_targets, "combine_embeddings")[1]
+    d_content = torch.empty((total, D), dtype=d_out.dtype, device=dev)
+    d_action = torch.empty((total, D), dtype=d_out.dtype, device=dev) if want_action else None
+    d_ctx = torch.empty((batch, contextual_len, D), dtype=d_out.dtype, device=dev) if contextual_len > 0 else None
+    with torch.cuda.device(dev):
+        L.check(L.lib().hstu_combine_embeddings_bwd(d_out.data_ptr(), so.data_ptr(), _vp(nt), oo.data_ptr(), d_content.data_ptr(),
+                                                    _vp(d_action), _vp(d_ctx), total_uih_len, total_targets, batch,
+                                                    contextual_len, D, mode, L.torch_dtype_code(d_out.dtype),
+                                                    L.index_dtype_code(so), L.current_stream_ptr(dev)))
+    return d_content, d_action, d_ctx

@@ -537,6 +537,63 @@ int hstu_multitask_head_bwd(const float* grad_loss, const float* grad_pred, cons
                             int64_t rows, int32_t dim, int32_t num_tasks, int32_t num_binary, float loss_scale, int dtype,
                             void* stream);
 
+/* ---- input preprocessors: the action encoder and the content / action / contextual combine as two row passes ----
+ * Action encode (ActionEncoder.forward, modules/action_encoder.py:73-112).  User b owns the UIH rows
+ * [uih_offsets[b], uih_offsets[b+1]) of `actions` / `watchtimes` (int64) and target_offsets[b+1] - target_offsets[b]
+ * target rows; its output rows start at uih_offsets[b] + target_offsets[b], UIH rows first.  For UIH row r
+ *   a = actions[r] | OR_k (watchtimes[r] >= thresholds[k] ? threshold_weights[k] : 0)
+ * and column block t (embedding_dim columns) of the output row is table[t, :] when (a & weights[t]) > 0 and 0 * table[t, :]
+ * otherwise (the reference multiplies the boolean into the table: a zero that keeps the parameter's sign); a target row
+ * is target_table.  table (num_types, embedding_dim) and target_table (num_types * embedding_dim)
+ * are fp32 device tensors, the output (total_uih_len + total_targets, num_types * embedding_dim) is contiguous in `dtype`
+ * (bf16 / fp16 / fp32): every value is a parameter rounded once, or zero.  weights (num_types <= 64), thresholds and
+ * threshold_weights (num_thresholds <= 64; watchtimes may be NULL without thresholds) are HOST arrays that travel as
+ * kernel arguments.  Offsets int32 or int64 (`index_dtype`).  Replaces two torch bit ops, a (rows, T, Da) fp32 product, a
+ * tile, a cast and concat_2D_jagged.  batch == 0 or no rows: returns without a launch.  No host synchronisation. */
+#define HSTU_ACTION_ENCODE_MAX_TYPES 64
+int hstu_action_encode_fwd(const int64_t* actions, const int64_t* watchtimes, const void* uih_offsets,
+                           const void* target_offsets, const float* table, const float* target_table, const int64_t* weights,
+                           int32_t num_types, const int64_t* thresholds, const int64_t* threshold_weights,
+                           int32_t num_thresholds, void* out, int64_t total_uih_len, int64_t total_targets, int32_t batch,
+                           int32_t embedding_dim, int dtype, int index_dtype, void* stream);
+/* d_table[t, c] = the sum of d_out[row, t * embedding_dim + c] over the UIH rows whose bit t is set, d_target_table[c'] =
+ * the sum of d_out[row, c'] over the target rows; fp32, fixed order (per-workgroup partials over fixed row slabs in
+ * `workspace`, then one sum over the workgroups): no float atomics, bit-identical run to run.  `workspace`:
+ * hstu_action_encode_bwd_workspace_bytes(rows, num_types * embedding_dim) bytes of device memory, 16-byte aligned.
+ * No rows: both gradients are zeroed. */
+size_t hstu_action_encode_bwd_workspace_bytes(int64_t total_rows, int32_t width);
+int hstu_action_encode_bwd(const void* d_out, const int64_t* actions, const int64_t* watchtimes, const void* uih_offsets,
+                           const void* target_offsets, const int64_t* weights, int32_t num_types, const int64_t* thresholds,
+                           const int64_t* threshold_weights, int32_t num_thresholds, float* d_table, float* d_target_table,
+                           void* workspace, int64_t total_uih_len, int64_t total_targets, int32_t batch, int32_t embedding_dim,
+                           int dtype, int index_dtype, void* stream);
+/* Combine (ContextualInterleavePreprocessor.combine_embeddings, modules/contextual_interleave_preprocessor.py:101-224).
+ * User b has L = seq_offsets[b+1] - seq_offsets[b] rows of content / action (total, dim), T = num_targets[b] of them
+ * targets (the last ones), U = L - T.  Its output rows start at out_offsets[b]; row j is contextual[b, j] with timestamp 0
+ * for j < contextual_len, and with p = j - contextual_len, o = seq_offsets[b]:
+ *   HSTU_COMBINE_SUM              content[o + p] + action[o + p] (fp32 add, one rounding; content alone when action is
+ *                                 NULL); contextual_len + L rows
+ *   HSTU_COMBINE_INTERLEAVE_ALL   row p >> 1 of content (p even) or action (p odd); contextual_len + 2 L rows
+ *   HSTU_COMBINE_INTERLEAVE_UIH   the same for p < 2 U, then content[o + U + (p - 2 U)]; contextual_len + 2 L - T rows
+ * and the timestamp (int64) of the source row.  out_offsets is the complete cumsum of those lengths, computed by the
+ * caller (hstu_complete_cumsum); the number of output rows follows from total_uih_len, total_targets, batch and
+ * contextual_len on the host.  num_targets (same integer type as the offsets) is read for INTERLEAVE_UIH only.  Replaces
+ * stack + mask + dense_to_jagged + boolean indexing (a host sync) + two concat_2D_jagged.  Bit-exact; no host sync. */
+#define HSTU_COMBINE_SUM 0
+#define HSTU_COMBINE_INTERLEAVE_ALL 1
+#define HSTU_COMBINE_INTERLEAVE_UIH 2
+int hstu_combine_embeddings_fwd(const void* content, const void* action, const void* contextual, const int64_t* timestamps,
+                                const void* seq_offsets, const void* num_targets, const void* out_offsets, void* out,
+                                int64_t* out_timestamps, int64_t total_uih_len, int64_t total_targets, int32_t batch,
+                                int32_t contextual_len, int32_t dim, int mode, int dtype, int index_dtype, void* stream);
+/* The inverse gather: every content / action / contextual row reads the one output row that copied it (SUM: content and
+ * action the same row; INTERLEAVE_UIH: the target rows of d_action are zeroed).  d_action / d_contextual may be NULL.  No
+ * atomics, no workspace, bit-exact. */
+int hstu_combine_embeddings_bwd(const void* d_out, const void* seq_offsets, const void* num_targets, const void* out_offsets,
+                                void* d_content, void* d_action, void* d_contextual, int64_t total_uih_len,
+                                int64_t total_targets, int32_t batch, int32_t contextual_len, int32_t dim, int mode, int dtype,
+                                int index_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
