@@ -12,6 +12,9 @@ constexpr int kNormWaves = kNormThreads / 64;
 // (the kernels of the layer's own row passes take the chunk count as a template parameter MC and are also instantiated
 // with MC = 1 -- a row of up to 64 pieces, e.g. 512 bf16 -- where the second chunk's registers would only cost occupancy)
 template <int VEC> constexpr int max_chunks() { return NORM_WIDE * (VEC == 8 ? 2 : (VEC == 4 ? 4 : 8)); }
+// (norm_dispatch.h picks the instance from these capacities: the two must not drift apart)
+static_assert(max_chunks<8>() == norm_dispatch::pieces_per_lane(8, NORM_WIDE == 4) && max_chunks<4>() == norm_dispatch::pieces_per_lane(4, NORM_WIDE == 4) &&
+              max_chunks<1>() == norm_dispatch::pieces_per_lane(1, NORM_WIDE == 4), "norm_dispatch.h and max_chunks() disagree");
 constexpr int kMaxNormBlocks = 2048;
 
 template <typename T, int VEC> struct RowVec {
@@ -807,12 +810,6 @@ __global__ __launch_bounds__(kNormThreads, (MC == 1 ? 5 : 1)) void norm_mul_bwd_
   }
 }
 
-static bool gn_fast_ok(int hdim, int v) {
-  if (v <= 1 || hdim % v) return false;
-  const int lph = hdim / v;
-  return lph <= 64 && (lph & (lph - 1)) == 0;
-}
-
 // ------------------------------------------------------------------ SiLU on a column slice
 template <typename T, bool BWD>
 __global__ void silu_kernel(const T* dout, const T* in, T* out, int64_t rows, int cols, int64_t s_dout, int64_t s_in,
@@ -848,18 +845,9 @@ static int norm_blocks_resident(K kernel, size_t lds, int64_t rows) {
   return (int)(resident < nb ? resident : nb);
 }
 
-template <typename T> static int vec_for(int dim, const void* a, const void* b2, const void* c) {
-  const int v = sizeof(T) == 2 ? 8 : 4;
-  const uintptr_t bits = (uintptr_t)a | (uintptr_t)b2 | (uintptr_t)c;
-  return (dim % v == 0 && (bits & 15) == 0) ? v : 1;
-}
-
-static int check_dim(int dim, int vec, const char* who) {
-  if (dim <= 0) return set_error(HSTU_EINVAL, "%s: dim must be positive", who);
-  const int lim = 64 * vec * NORM_WIDE * (vec == 8 ? 2 : (vec == 4 ? 4 : 8));
-  if (dim > lim) return set_error(HSTU_EUNSUPPORTED, "%s: dim %d exceeds the %d supported with this alignment", who, dim, lim);
-  return HSTU_OK;
-}
+// The launchers below take the class of the call (piece width, chunk class, group-norm path) from norm_ops.hip, which
+// decided it -- and this instance, and whether the row is accepted at all -- with norm_dispatch.h; nothing is derived here.
+using norm_dispatch::RowClass;
 
 // Launch of a row kernel on the grid that is resident at once (nb: out, the bwd launchers hand it to the reduction).
 #define ROW_LAUNCH(NB, LDS, K, ...)                                                        \
@@ -869,37 +857,33 @@ static int check_dim(int dim, int vec, const char* who) {
   } while (0)
 
 template <typename T, bool SWISH = false>
-static int ln_fwd(const void* x, const void* w, const void* b, void* y, float* mean, float* rstd, int64_t rows, int dim,
-                  float eps, hipStream_t st) {
+static int ln_fwd(const RowClass& cls, const void* x, const void* w, const void* b, void* y, float* mean, float* rstd,
+                  int64_t rows, int dim, float eps, hipStream_t st) {
   const char* who = SWISH ? "swish_layer_norm_fwd" : "layer_norm_fwd";
-  const int v = vec_for<T>(dim, x, y, w) == 1 ? 1 : vec_for<T>(dim, b, nullptr, nullptr);
-  if (int e = check_dim(dim, v, who)) return e;
+  const int v = cls.vec;
   constexpr int VV = sizeof(T) == 2 ? 8 : 4;
   int nb;
 #define LN_ARGS (const T*)x, (const T*)w, (const T*)b, (T*)y, mean, rstd, rows, dim, eps
   if (v == 1) ROW_LAUNCH(nb, 0, (layer_norm_fwd_kernel<T, 1, max_chunks<1>(), SWISH>), LN_ARGS);
-  else if (dim <= 64 * VV) ROW_LAUNCH(nb, 0, (layer_norm_fwd_kernel<T, VV, 1, SWISH>), LN_ARGS);
+  else if (cls.one_chunk) ROW_LAUNCH(nb, 0, (layer_norm_fwd_kernel<T, VV, 1, SWISH>), LN_ARGS);
   else ROW_LAUNCH(nb, 0, (layer_norm_fwd_kernel<T, VV, max_chunks<VV>(), SWISH>), LN_ARGS);
 #undef LN_ARGS
   return check_launch(who);
 }
 
 template <typename T, bool SWISH = false>
-static int ln_bwd(const void* dy, const void* x, const void* w, const float* mean, const float* rstd, void* dx,
-                  float* dweight, float* dbias, float* partial, int64_t rows, int dim, const void* dres, hipStream_t st,
-                  const void* b = nullptr) {
+static int ln_bwd(const RowClass& cls, const void* dy, const void* x, const void* w, const float* mean, const float* rstd,
+                  void* dx, float* dweight, float* dbias, float* partial, int64_t rows, int dim, const void* dres,
+                  hipStream_t st, const void* b = nullptr) {
   const char* who = SWISH ? "swish_layer_norm_bwd" : "layer_norm_bwd";
-  int v = vec_for<T>(dim, dy, x, dx);
-  if (v != 1 && dres) v = vec_for<T>(dim, dres, nullptr, nullptr);
-  if (v != 1) v = vec_for<T>(dim, w, b, nullptr);
-  if (int e = check_dim(dim, v, who)) return e;
+  const int v = cls.vec;
   constexpr int VV = sizeof(T) == 2 ? 8 : 4;
   const int nch = (dim + 64 * v - 1) / (64 * v);
   const size_t lds = (size_t)kNormWaves * nch * 64 * v * sizeof(float);
   int nb;
 #define LN_ARGS (const T*)dy, (const T*)x, (const T*)w, mean, rstd, (T*)dx, partial, rows, dim, (const T*)dres, (const T*)b
   if (v == 1) ROW_LAUNCH(nb, lds, (layer_norm_bwd_kernel<T, 1, max_chunks<1>(), SWISH>), LN_ARGS);
-  else if (nch == 1) ROW_LAUNCH(nb, lds, (layer_norm_bwd_kernel<T, VV, 1, SWISH>), LN_ARGS);
+  else if (cls.one_chunk) ROW_LAUNCH(nb, lds, (layer_norm_bwd_kernel<T, VV, 1, SWISH>), LN_ARGS);
   else ROW_LAUNCH(nb, lds, (layer_norm_bwd_kernel<T, VV, max_chunks<VV>(), SWISH>), LN_ARGS);
 #undef LN_ARGS
   if (int e = check_launch(who)) return e;
@@ -908,23 +892,18 @@ static int ln_bwd(const void* dy, const void* x, const void* w, const float* mea
 }
 
 template <typename T>
-static int nm_fwd(const void* attn, const void* u, const void* w, const void* b, void* y, float* mean, float* rstd,
+static int nm_fwd(const RowClass& cls, const void* attn, const void* u, const void* w, const void* b, void* y, float* mean, float* rstd,
                   int64_t rows, int heads, int hdim, float eps, int gn, int concat, DropCtx dc, int64_t u_stride, bool silu,
                   hipStream_t st) {
-  const int dim = heads * hdim;
-  int v = vec_for<T>(dim, attn, u, y);
-  if ((u_stride * (int64_t)sizeof(T)) % 16) v = 1;
+  const int v = cls.vec;
   const USrc us{u_stride, 0};
-  if (v != 1 && !gn) v = vec_for<T>(dim, w, b, nullptr);
-  if (v != 1 && gn && hdim % v) v = 1;
-  if (int e = check_dim(dim, v, "norm_mul_fwd")) return e;
   if (gn && heads > 16) return set_error(HSTU_EUNSUPPORTED, "norm_mul: group norm supports at most 16 heads");
   constexpr int VV = sizeof(T) == 2 ? 8 : 4;
   int nb;
 #define NM_ARGS (const T*)attn, (const T*)u, (const T*)w, (const T*)b, (T*)y, mean, rstd, rows, heads, hdim, eps, concat, dc, us
 #define NM_PICK(S)                                                                                                              \
-  if (gn && gn_fast_ok(hdim, v) && dim <= 64 * VV) ROW_LAUNCH(nb, 0, (norm_mul_fwd_gn_kernel<T, VV, 1, S>), NM_ARGS);              \
-  else if (gn && gn_fast_ok(hdim, v)) ROW_LAUNCH(nb, 0, (norm_mul_fwd_gn_kernel<T, VV, max_chunks<VV>(), S>), NM_ARGS);            \
+  if (cls.gn_fast && cls.one_chunk) ROW_LAUNCH(nb, 0, (norm_mul_fwd_gn_kernel<T, VV, 1, S>), NM_ARGS);              \
+  else if (cls.gn_fast) ROW_LAUNCH(nb, 0, (norm_mul_fwd_gn_kernel<T, VV, max_chunks<VV>(), S>), NM_ARGS);            \
   else if (v == 1 && gn) ROW_LAUNCH(nb, 0, (norm_mul_fwd_kernel<T, 1, true, S>), NM_ARGS);                                         \
   else if (v == 1) ROW_LAUNCH(nb, 0, (norm_mul_fwd_kernel<T, 1, false, S>), NM_ARGS);                                              \
   else if (gn) ROW_LAUNCH(nb, 0, (norm_mul_fwd_kernel<T, VV, true, S>), NM_ARGS);                                                  \
@@ -936,18 +915,13 @@ static int nm_fwd(const void* attn, const void* u, const void* w, const void* b,
 }
 
 template <typename T>
-static int nm_bwd(const void* dy, const void* attn, const void* u, const void* w, const void* b, const float* mean,
+static int nm_bwd(const RowClass& cls, const void* dy, const void* attn, const void* u, const void* w, const void* b, const float* mean,
                   const float* rstd, void* dattn, void* du, float* dweight, float* dbias, float* partial, int64_t rows,
                   int heads, int hdim, int gn, int concat, DropCtx dc, int64_t u_stride, int64_t du_stride, bool silu,
                   hipStream_t st) {
   const int dim = heads * hdim;
-  int v = vec_for<T>(dim, attn, u, dy);
-  if (v != 1) v = vec_for<T>(dim, dattn, du, nullptr);
-  if (((u_stride | du_stride) * (int64_t)sizeof(T)) % 16) v = 1;
+  const int v = cls.vec;
   const USrc us{u_stride, du_stride};
-  if (v != 1 && !gn) v = vec_for<T>(dim, w, b, nullptr);
-  if (v != 1 && gn && hdim % v) v = 1;
-  if (int e = check_dim(dim, v, "norm_mul_bwd")) return e;
   if (gn && heads > 16) return set_error(HSTU_EUNSUPPORTED, "norm_mul: group norm supports at most 16 heads");
   constexpr int VV = sizeof(T) == 2 ? 8 : 4;
   const int nch = (dim + 64 * v - 1) / (64 * v);
@@ -955,8 +929,8 @@ static int nm_bwd(const void* dy, const void* attn, const void* u, const void* w
   int nb;
 #define NM_ARGS (const T*)dy, (const T*)attn, (const T*)u, (const T*)w, (const T*)b, mean, rstd, (T*)dattn, (T*)du, partial, rows, heads, hdim, concat, dc, us
 #define NM_PICK(S)                                                                                                              \
-  if (gn && gn_fast_ok(hdim, v) && dim <= 64 * VV) ROW_LAUNCH(nb, lds, (norm_mul_bwd_gn_kernel<T, VV, 1, S>), NM_ARGS);            \
-  else if (gn && gn_fast_ok(hdim, v)) ROW_LAUNCH(nb, lds, (norm_mul_bwd_gn_kernel<T, VV, max_chunks<VV>(), S>), NM_ARGS);          \
+  if (cls.gn_fast && cls.one_chunk) ROW_LAUNCH(nb, lds, (norm_mul_bwd_gn_kernel<T, VV, 1, S>), NM_ARGS);            \
+  else if (cls.gn_fast) ROW_LAUNCH(nb, lds, (norm_mul_bwd_gn_kernel<T, VV, max_chunks<VV>(), S>), NM_ARGS);          \
   else if (v == 1 && gn) ROW_LAUNCH(nb, lds, (norm_mul_bwd_kernel<T, 1, true, S>), NM_ARGS);                                       \
   else if (v == 1) ROW_LAUNCH(nb, lds, (norm_mul_bwd_kernel<T, 1, false, S>), NM_ARGS);                                            \
   else if (gn) ROW_LAUNCH(nb, lds, (norm_mul_bwd_kernel<T, VV, true, S>), NM_ARGS);                                                \
@@ -993,13 +967,11 @@ __global__ __launch_bounds__(256) void silu_vec_kernel(const T* dout, const T* i
 }
 
 template <typename T, bool BWD>
-static int silu_launch(const void* dout, const void* in, void* out, int64_t rows, int cols, int64_t s0, int64_t s1,
-                       int64_t s2, hipStream_t st) {
+static int silu_launch(bool vec_ok, const void* dout, const void* in, void* out, int64_t rows, int cols, int64_t s0,
+                       int64_t s1, int64_t s2, hipStream_t st) {
   const int64_t n = rows * cols;
   if (n == 0) return HSTU_OK;
   constexpr int VEC = 16 / sizeof(T);
-  const bool vec_ok = cols % VEC == 0 && s1 % VEC == 0 && s2 % VEC == 0 && (!BWD || s0 % VEC == 0) &&
-                      (((uintptr_t)in | (uintptr_t)out | (BWD ? (uintptr_t)dout : 0)) & 15) == 0;
   if (vec_ok) {
     const int64_t pieces = n / VEC;
     int blocks = (int)((pieces + 255) / 256);
@@ -1052,10 +1024,9 @@ __global__ __launch_bounds__(kNormThreads) void l2_norm_kernel(const T* x, const
 }
 
 template <typename T, bool BWD>
-static int l2_launch(const void* x, const void* g, void* out, int64_t rows, int dim, float eps, hipStream_t st) {
-  if (rows == 0) return HSTU_OK;
-  const int v = vec_for<T>(dim, x, BWD ? g : x, out);
-  if (int e = check_dim(dim, v, "l2_norm")) return e;
+static int l2_launch(const RowClass& cls, const void* x, const void* g, void* out, int64_t rows, int dim, float eps,
+                     hipStream_t st) {
+  const int v = cls.vec;
   int nb;
   constexpr int VV = sizeof(T) == 2 ? 8 : 4;
   if (v == 1) ROW_LAUNCH(nb, 0, (l2_norm_kernel<T, 1, BWD>), (const T*)x, (const T*)g, (T*)out, rows, dim, eps);

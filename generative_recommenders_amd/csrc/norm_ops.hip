@@ -11,6 +11,7 @@
 // ops/triton/triton_hstu_linear.py:48-337 (LN * u), :570-1036 (GroupNorm * u).
 #include "hstu_common.cuh"
 #include "capi_internal.h"
+#include "norm_dispatch.h"
 
 namespace hstu {
 // narrow / wide instances of every kernel and launcher (norm_kernels.inc)
@@ -24,14 +25,19 @@ namespace nw4 {
 #include "norm_kernels.inc"
 #undef NORM_WIDE
 }  // namespace nw4
-// rows of up to 1024 elements (512 without 16-byte alignment) take the narrow instance
-static bool norm_wide(int dim, const void* a, const void* b, const void* c, int elem_bytes) {
-  const int v = 16 / elem_bytes;
-  const bool aligned = dim % v == 0 && ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0);
-  return dim > (aligned ? 1024 : 512);
-}
+// Every entry point below asks norm_dispatch.h ONCE for the class of its call -- piece width from all the facts its
+// kernels depend on, then the narrow instance for rows of up to 1024 elements at the vector width (512 at the scalar
+// width) and the wide one above, refused past 4096 (2048) -- and passes that class on to the instance's launcher.
 using nw1::kMaxNormBlocks;
 using nw1::silu_launch;
+using norm_dispatch::RowClass;
+static int elem_bytes_of(int dtype) { return dtype == HSTU_DTYPE_F32 ? 4 : 2; }
+static int accept_row(const RowClass& k, int dim, const char* who) {
+  if (dim <= 0) return set_error(HSTU_EINVAL, "%s: dim must be positive", who);
+  if (norm_dispatch::refused(k, dim))
+    return set_error(HSTU_EUNSUPPORTED, "%s: dim %d exceeds the %d supported with this alignment", who, dim, k.limit);
+  return HSTU_OK;
+}
 }  // namespace hstu
 
 using namespace hstu;
@@ -44,8 +50,8 @@ using namespace hstu;
     default: return set_error(HSTU_EINVAL, "dtype must be bf16, fp16 or fp32");       \
   }
 
-// (wide ? nw4::CALL : nw1::CALL): the row kernels' narrow or wide instance
-#define NW(wide, ...) ((wide) ? nw4::__VA_ARGS__ : nw1::__VA_ARGS__)
+// (cls.wide ? nw4::CALL : nw1::CALL): the row kernels' narrow or wide instance
+#define NW(cls, ...) ((cls).wide ? nw4::__VA_ARGS__ : nw1::__VA_ARGS__)
 
 extern "C" {
 
@@ -59,10 +65,11 @@ int hstu_layer_norm_fwd(const void* x, const void* weight, const void* bias, voi
   if (rows == 0) return HSTU_OK;
   if (!x || !weight || !bias || !y) return set_error(HSTU_EINVAL, "layer_norm_fwd: NULL tensor");
   hipStream_t st = (hipStream_t)stream;
-  const bool wd = norm_wide(dim, x, y, weight, dtype == HSTU_DTYPE_F32 ? 4 : 2);
-  DISPATCH_DTYPE(dtype, NW(wd, ln_fwd<bf16_t>(x, weight, bias, y, mean, rstd, rows, dim, eps, st)),
-                 NW(wd, ln_fwd<f16_t>(x, weight, bias, y, mean, rstd, rows, dim, eps, st)),
-                 NW(wd, ln_fwd<float>(x, weight, bias, y, mean, rstd, rows, dim, eps, st)));
+  const RowClass k = norm_dispatch::ln_fwd_class(dim, elem_bytes_of(dtype), x, weight, bias, y);
+  if (int e = accept_row(k, dim, "layer_norm_fwd")) return e;
+  DISPATCH_DTYPE(dtype, NW(k, ln_fwd<bf16_t>(k, x, weight, bias, y, mean, rstd, rows, dim, eps, st)),
+                 NW(k, ln_fwd<f16_t>(k, x, weight, bias, y, mean, rstd, rows, dim, eps, st)),
+                 NW(k, ln_fwd<float>(k, x, weight, bias, y, mean, rstd, rows, dim, eps, st)));
 }
 
 int hstu_layer_norm_bwd(const void* dy, const void* x, const void* weight, const float* mean, const float* rstd,
@@ -83,10 +90,11 @@ int hstu_layer_norm_bwd_residual(const void* dy, const void* x, const void* weig
     return HSTU_OK;
   }
   if (!dy || !x || !weight || !mean || !rstd || !dx || !partial_ws) return set_error(HSTU_EINVAL, "layer_norm_bwd: NULL tensor");
-  const bool wd = norm_wide(dim, dy, x, dx, dtype == HSTU_DTYPE_F32 ? 4 : 2);
-  DISPATCH_DTYPE(dtype, NW(wd, ln_bwd<bf16_t>(dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, dres, st)),
-                 NW(wd, ln_bwd<f16_t>(dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, dres, st)),
-                 NW(wd, ln_bwd<float>(dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, dres, st)));
+  const RowClass k = norm_dispatch::ln_bwd_class(dim, elem_bytes_of(dtype), dy, x, weight, nullptr, dres, dx);
+  if (int e = accept_row(k, dim, "layer_norm_bwd")) return e;
+  DISPATCH_DTYPE(dtype, NW(k, ln_bwd<bf16_t>(k, dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, dres, st)),
+                 NW(k, ln_bwd<f16_t>(k, dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, dres, st)),
+                 NW(k, ln_bwd<float>(k, dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, dres, st)));
 }
 
 // y = x * sigmoid(LayerNorm(x)): the gate in front of the preprocessors' and DlrmHSTU's MLPs (SwishLayerNorm)
@@ -95,10 +103,11 @@ int hstu_swish_layer_norm_fwd(const void* x, const void* weight, const void* bia
   if (rows == 0) return HSTU_OK;
   if (!x || !weight || !bias || !y) return set_error(HSTU_EINVAL, "swish_layer_norm_fwd: NULL tensor");
   hipStream_t st = (hipStream_t)stream;
-  const bool wd = norm_wide(dim, x, y, weight, dtype == HSTU_DTYPE_F32 ? 4 : 2);
-  DISPATCH_DTYPE(dtype, NW(wd, ln_fwd<bf16_t, true>(x, weight, bias, y, mean, rstd, rows, dim, eps, st)),
-                 NW(wd, ln_fwd<f16_t, true>(x, weight, bias, y, mean, rstd, rows, dim, eps, st)),
-                 NW(wd, ln_fwd<float, true>(x, weight, bias, y, mean, rstd, rows, dim, eps, st)));
+  const RowClass k = norm_dispatch::ln_fwd_class(dim, elem_bytes_of(dtype), x, weight, bias, y);
+  if (int e = accept_row(k, dim, "swish_layer_norm_fwd")) return e;
+  DISPATCH_DTYPE(dtype, NW(k, ln_fwd<bf16_t, true>(k, x, weight, bias, y, mean, rstd, rows, dim, eps, st)),
+                 NW(k, ln_fwd<f16_t, true>(k, x, weight, bias, y, mean, rstd, rows, dim, eps, st)),
+                 NW(k, ln_fwd<float, true>(k, x, weight, bias, y, mean, rstd, rows, dim, eps, st)));
 }
 
 int hstu_swish_layer_norm_bwd(const void* dy, const void* x, const void* weight, const void* bias, const float* mean,
@@ -112,10 +121,11 @@ int hstu_swish_layer_norm_bwd(const void* dy, const void* x, const void* weight,
     return HSTU_OK;
   }
   if (!dy || !x || !weight || !bias || !mean || !rstd || !dx || !partial_ws) return set_error(HSTU_EINVAL, "swish_layer_norm_bwd: NULL tensor");
-  const bool wd = norm_wide(dim, dy, x, dx, dtype == HSTU_DTYPE_F32 ? 4 : 2);
-  DISPATCH_DTYPE(dtype, NW(wd, ln_bwd<bf16_t, true>(dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, nullptr, st, bias)),
-                 NW(wd, ln_bwd<f16_t, true>(dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, nullptr, st, bias)),
-                 NW(wd, ln_bwd<float, true>(dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, nullptr, st, bias)));
+  const RowClass k = norm_dispatch::ln_bwd_class(dim, elem_bytes_of(dtype), dy, x, weight, bias, nullptr, dx);
+  if (int e = accept_row(k, dim, "swish_layer_norm_bwd")) return e;
+  DISPATCH_DTYPE(dtype, NW(k, ln_bwd<bf16_t, true>(k, dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, nullptr, st, bias)),
+                 NW(k, ln_bwd<f16_t, true>(k, dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, nullptr, st, bias)),
+                 NW(k, ln_bwd<float, true>(k, dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, nullptr, st, bias)));
 }
 
 static int drop_ratio_ok(float r, const char* who) {
@@ -140,9 +150,10 @@ int hstu_norm_mul_silu_fwd(const void* attn, const void* u, int64_t u_row_stride
   if (rows == 0) return HSTU_OK;
   if (!attn || !u || !weight || !bias || !y) return set_error(HSTU_EINVAL, "norm_mul_fwd: NULL tensor");
   hipStream_t st = (hipStream_t)stream;
-  const bool wd = norm_wide(heads * head_dim, attn, u, y, dtype == HSTU_DTYPE_F32 ? 4 : 2);
-#define NM_FWD(T) (wd ? nw4::nm_fwd<T>(attn, u, weight, bias, y, mean, rstd, rows, heads, head_dim, eps, group_norm, concat_ux, nw4::make_drop_ctx(dropout_ratio, seed), u_row_stride, silu, st) \
-                      : nw1::nm_fwd<T>(attn, u, weight, bias, y, mean, rstd, rows, heads, head_dim, eps, group_norm, concat_ux, nw1::make_drop_ctx(dropout_ratio, seed), u_row_stride, silu, st))
+  const RowClass k = norm_dispatch::nm_fwd_class(heads, head_dim, elem_bytes_of(dtype), group_norm != 0, attn, u, u_row_stride, weight, bias, y);
+  if (int e = accept_row(k, heads * head_dim, "norm_mul_fwd")) return e;
+#define NM_FWD(T) (k.wide ? nw4::nm_fwd<T>(k, attn, u, weight, bias, y, mean, rstd, rows, heads, head_dim, eps, group_norm, concat_ux, nw4::make_drop_ctx(dropout_ratio, seed), u_row_stride, silu, st) \
+                      : nw1::nm_fwd<T>(k, attn, u, weight, bias, y, mean, rstd, rows, heads, head_dim, eps, group_norm, concat_ux, nw1::make_drop_ctx(dropout_ratio, seed), u_row_stride, silu, st))
   DISPATCH_DTYPE(dtype, NM_FWD(bf16_t), NM_FWD(f16_t), NM_FWD(float));
 #undef NM_FWD
 }
@@ -190,10 +201,11 @@ int hstu_norm_mul_silu_bwd(const void* dy, const void* attn, const void* u, int6
   }
   if (!dy || !attn || !u || !weight || !bias || !mean || !rstd || !dattn || !du || !partial_ws)
     return set_error(HSTU_EINVAL, "norm_mul_bwd: NULL tensor");
-  const bool wd = norm_wide(heads * head_dim, attn, u, dy, dtype == HSTU_DTYPE_F32 ? 4 : 2) ||
-                  norm_wide(heads * head_dim, dattn, du, nullptr, dtype == HSTU_DTYPE_F32 ? 4 : 2);
-#define NM_BWD(T) (wd ? nw4::nm_bwd<T>(dy, attn, u, weight, bias, mean, rstd, dattn, du, dweight, dbias, partial_ws, rows, heads, head_dim, group_norm, concat_ux, nw4::make_drop_ctx(dropout_ratio, seed), u_row_stride, du_row_stride, silu, st) \
-                      : nw1::nm_bwd<T>(dy, attn, u, weight, bias, mean, rstd, dattn, du, dweight, dbias, partial_ws, rows, heads, head_dim, group_norm, concat_ux, nw1::make_drop_ctx(dropout_ratio, seed), u_row_stride, du_row_stride, silu, st))
+  const RowClass k = norm_dispatch::nm_bwd_class(heads, head_dim, elem_bytes_of(dtype), group_norm != 0, dy, attn, u, u_row_stride, weight, bias,
+                                                 dattn, du, du_row_stride);
+  if (int e = accept_row(k, heads * head_dim, "norm_mul_bwd")) return e;
+#define NM_BWD(T) (k.wide ? nw4::nm_bwd<T>(k, dy, attn, u, weight, bias, mean, rstd, dattn, du, dweight, dbias, partial_ws, rows, heads, head_dim, group_norm, concat_ux, nw4::make_drop_ctx(dropout_ratio, seed), u_row_stride, du_row_stride, silu, st) \
+                      : nw1::nm_bwd<T>(k, dy, attn, u, weight, bias, mean, rstd, dattn, du, dweight, dbias, partial_ws, rows, heads, head_dim, group_norm, concat_ux, nw1::make_drop_ctx(dropout_ratio, seed), u_row_stride, du_row_stride, silu, st))
   DISPATCH_DTYPE(dtype, NM_BWD(bf16_t), NM_BWD(f16_t), NM_BWD(float));
 #undef NM_BWD
 }
@@ -201,36 +213,42 @@ int hstu_norm_mul_silu_bwd(const void* dy, const void* attn, const void* u, int6
 int hstu_silu_fwd(const void* in, void* out, int64_t rows, int32_t cols, int64_t in_row_stride, int64_t out_row_stride,
                   int dtype, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  DISPATCH_DTYPE(dtype, (silu_launch<bf16_t, false>(nullptr, in, out, rows, cols, 0, in_row_stride, out_row_stride, st)),
-                 (silu_launch<f16_t, false>(nullptr, in, out, rows, cols, 0, in_row_stride, out_row_stride, st)),
-                 (silu_launch<float, false>(nullptr, in, out, rows, cols, 0, in_row_stride, out_row_stride, st)));
+  const bool vk = norm_dispatch::silu_vector(elem_bytes_of(dtype), cols, nullptr, in, out, 0, in_row_stride, out_row_stride);
+  DISPATCH_DTYPE(dtype, (silu_launch<bf16_t, false>(vk, nullptr, in, out, rows, cols, 0, in_row_stride, out_row_stride, st)),
+                 (silu_launch<f16_t, false>(vk, nullptr, in, out, rows, cols, 0, in_row_stride, out_row_stride, st)),
+                 (silu_launch<float, false>(vk, nullptr, in, out, rows, cols, 0, in_row_stride, out_row_stride, st)));
 }
 
 int hstu_silu_bwd(const void* dout, const void* in, void* din, int64_t rows, int32_t cols, int64_t dout_row_stride,
                   int64_t in_row_stride, int64_t din_row_stride, int dtype, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  DISPATCH_DTYPE(dtype, (silu_launch<bf16_t, true>(dout, in, din, rows, cols, dout_row_stride, in_row_stride, din_row_stride, st)),
-                 (silu_launch<f16_t, true>(dout, in, din, rows, cols, dout_row_stride, in_row_stride, din_row_stride, st)),
-                 (silu_launch<float, true>(dout, in, din, rows, cols, dout_row_stride, in_row_stride, din_row_stride, st)));
+  const bool vk = norm_dispatch::silu_vector(elem_bytes_of(dtype), cols, dout, in, din, dout_row_stride, in_row_stride, din_row_stride);
+  DISPATCH_DTYPE(dtype, (silu_launch<bf16_t, true>(vk, dout, in, din, rows, cols, dout_row_stride, in_row_stride, din_row_stride, st)),
+                 (silu_launch<f16_t, true>(vk, dout, in, din, rows, cols, dout_row_stride, in_row_stride, din_row_stride, st)),
+                 (silu_launch<float, true>(vk, dout, in, din, rows, cols, dout_row_stride, in_row_stride, din_row_stride, st)));
 }
 
 
 int hstu_l2_norm_fwd(const void* x, void* y, int64_t rows, int32_t dim, float eps, int dtype, void* stream) {
   if (rows > 0 && (!x || !y)) return set_error(HSTU_EINVAL, "hstu_l2_norm_fwd: x and y must be non-NULL");
   hipStream_t st = (hipStream_t)stream;
-  const bool wd = norm_wide(dim, x, y, nullptr, dtype == HSTU_DTYPE_F32 ? 4 : 2);
-  DISPATCH_DTYPE(dtype, NW(wd, l2_launch<bf16_t, false>(x, nullptr, y, rows, dim, eps, st)),
-                 NW(wd, l2_launch<f16_t, false>(x, nullptr, y, rows, dim, eps, st)),
-                 NW(wd, l2_launch<float, false>(x, nullptr, y, rows, dim, eps, st)));
+  if (rows == 0) return HSTU_OK;
+  const RowClass k = norm_dispatch::l2_class(dim, elem_bytes_of(dtype), x, nullptr, y);
+  if (int e = accept_row(k, dim, "l2_norm")) return e;
+  DISPATCH_DTYPE(dtype, NW(k, l2_launch<bf16_t, false>(k, x, nullptr, y, rows, dim, eps, st)),
+                 NW(k, l2_launch<f16_t, false>(k, x, nullptr, y, rows, dim, eps, st)),
+                 NW(k, l2_launch<float, false>(k, x, nullptr, y, rows, dim, eps, st)));
 }
 
 int hstu_l2_norm_bwd(const void* dy, const void* x, void* dx, int64_t rows, int32_t dim, float eps, int dtype, void* stream) {
   if (rows > 0 && (!x || !dy || !dx)) return set_error(HSTU_EINVAL, "hstu_l2_norm_bwd: dy, x and dx must be non-NULL");
   hipStream_t st = (hipStream_t)stream;
-  const bool wd = norm_wide(dim, x, dy, dx, dtype == HSTU_DTYPE_F32 ? 4 : 2);
-  DISPATCH_DTYPE(dtype, NW(wd, l2_launch<bf16_t, true>(x, dy, dx, rows, dim, eps, st)),
-                 NW(wd, l2_launch<f16_t, true>(x, dy, dx, rows, dim, eps, st)),
-                 NW(wd, l2_launch<float, true>(x, dy, dx, rows, dim, eps, st)));
+  if (rows == 0) return HSTU_OK;
+  const RowClass k = norm_dispatch::l2_class(dim, elem_bytes_of(dtype), x, dy, dx);
+  if (int e = accept_row(k, dim, "l2_norm")) return e;
+  DISPATCH_DTYPE(dtype, NW(k, l2_launch<bf16_t, true>(k, x, dy, dx, rows, dim, eps, st)),
+                 NW(k, l2_launch<f16_t, true>(k, x, dy, dx, rows, dim, eps, st)),
+                 NW(k, l2_launch<float, true>(k, x, dy, dx, rows, dim, eps, st)));
 }
 
 }  // extern "C"

@@ -442,3 +442,22 @@ def test_silu_matches_torch():
     s = sl.clone().requires_grad_()
     torch.nn.functional.silu(s).backward(g)
     torch.testing.assert_close(_launch.silu_bwd(g, sl), s.grad, rtol=1e-5, atol=1e-6)
+    # against fp64, in every dtype, on the 16-byte-friendly slice above (the vector kernel) and on a slice whose start and
+    # row stride are no 16-byte multiples (the scalar kernel).  16-bit: within 2 x the largest error measured on MI355X,
+    # in ulps of the output type (tests/test_norm_classes_gpu.py, profiles/silu_16bit_ulp.md)
+    from test_norm_classes_gpu import SILU_ULP_MEASURED, _ulp_error
+
+    for dtype in (torch.float32, torch.bfloat16, torch.float16):
+        for cols, lo, hi in ((96, 16, 80), (99, 17, 82)):
+            xs = (3 * torch.randn(100, cols)).to(dtype).to(DEV)[:, lo:hi]
+            gs = torch.randn(100, hi - lo).to(dtype).to(DEV)
+            assert (xs.data_ptr() % 16 == 0 and (xs.stride(0) * xs.element_size()) % 16 == 0) == (cols == 96)
+            x64, g64 = xs.double().cpu().numpy(), gs.double().cpu().numpy()
+            sg = 1.0 / (1.0 + np.exp(-x64))
+            for got, ref in ((_launch.silu_fwd(xs), x64 * sg), (_launch.silu_bwd(gs, xs), g64 * sg * (1.0 + x64 * (1.0 - sg)))):
+                assert got.dtype == dtype and got.shape == xs.shape
+                got = got.double().cpu().numpy()
+                if dtype == torch.float32:
+                    np.testing.assert_allclose(got, ref, rtol=1e-5, atol=1e-6)
+                else:
+                    assert _ulp_error(got, ref, dtype).max() <= 2 * SILU_ULP_MEASURED[dtype]
