@@ -156,6 +156,11 @@ SIGNATURES = {
                                            _int, _vp]),
     "hstu_combine_embeddings_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _int, _int, _int,
                                            _vp]),
+    "hstu_time_features": (_int, [_vp, _vp, _vp, _i32, _vp, _i64, _vp]),
+    "hstu_time_ln_workspace_bytes": (C.c_size_t, [_i32, _i32]),
+    "hstu_time_ln_fwd": (_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _i32, _int, _vp]),
+    "hstu_time_ln_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32,
+                                _int, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -90,6 +90,18 @@ inline RowClass nm_bwd_class(int heads, int head_dim, int elem_bytes, bool group
 inline RowClass l2_class(int dim, int elem_bytes, const void* x, const void* g, const void* out) {
   return decide(Facts(dim, elem_bytes).ptr(x).ptr(g).ptr(out));
 }
+// the timestamp postprocessor's row pass (time_ln_ops.hip): z0 / y (dy / z0 / dz) rows in `elem_bytes` elements; b, wt,
+// ln_w, ln_b are fp32 and read in 16-byte pieces whenever the rows are, so their alignment is a fact of the call too
+// (dim % V == 0 keeps every row of wt aligned).  The backward's lanes hold one chunk whatever the width: it uses the
+// piece width and the limit of its class.
+inline RowClass time_ln_fwd_class(int dim, int elem_bytes, const void* z0, const void* b, const void* wt, const void* ln_w,
+                                  const void* ln_b, const void* y) {
+  return decide(Facts(dim, elem_bytes).ptr(z0).ptr(b).ptr(wt).ptr(ln_w).ptr(ln_b).ptr(y));
+}
+inline RowClass time_ln_bwd_class(int dim, int elem_bytes, const void* dy, const void* z0, const void* b, const void* wt,
+                                  const void* ln_w, const void* dz) {
+  return decide(Facts(dim, elem_bytes).ptr(dy).ptr(z0).ptr(b).ptr(wt).ptr(ln_w).ptr(dz));
+}
 // SiLU on a column slice is not register-resident (any width): the only choice is 16-byte pieces or scalars.
 // dout / s_dout: the backward's incoming gradient (forward: NULL / 0)
 inline bool silu_vector(int elem_bytes, int cols, const void* dout, const void* in, const void* out, int64_t s_dout,

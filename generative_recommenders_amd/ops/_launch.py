@@ -1151,3 +1151,76 @@ def combine_embeddings_bwd(d_out, seq_offsets, num_targets, out_offsets, mode: i
                                                     contextual_len, D, mode, L.torch_dtype_code(d_out.dtype),
                                                     L.index_dtype_code(so), L.current_stream_ptr(dev)))
     return d_content, d_action, d_ctx
+
+
+# ---- timestamp postprocessor (hstu_time_features / hstu_time_ln_*) ---------------------------------------------------
+TIME_LN_MAX_PERIODS = 4          # HSTU_TIME_LN_MAX_PERIODS
+
+
+def _periods(period_units: torch.Tensor, units_per_period: torch.Tensor, device):
+    """the module's (1, F) buffers as two contiguous fp32 device arrays of F numbers"""
+    pu = period_units.detach().reshape(-1).to(device=device, dtype=torch.float32).contiguous()
+    upp = units_per_period.detach().reshape(-1).to(device=device, dtype=torch.float32).contiguous()
+    torch._assert(pu.numel() == upp.numel(), "period_units and units_per_period must have one entry per period")
+    return pu, upp
+
+
+def time_ln_supported(dim: int, num_periods: int, dtype: torch.dtype) -> bool:
+    """whether the fused row pass takes rows of ``dim`` elements with ``num_periods`` periods: contiguous rows of fresh
+    allocations are 16-byte aligned, so the class is the vector one whenever dim is a multiple of the piece"""
+    if dtype not in (torch.bfloat16, torch.float16, torch.float32) or not 1 <= num_periods <= TIME_LN_MAX_PERIODS or dim < 1:
+        return False
+    piece = 4 if dtype == torch.float32 else 8
+    return dim <= (4096 if dim % piece == 0 else 2048)
+
+
+def time_features(timestamps: torch.Tensor, period_units: torch.Tensor, units_per_period: torch.Tensor) -> torch.Tensor:
+    """(rows, 2F) fp32 [cos, sin] per period of int64 timestamps: the reference's fp32 arithmetic (hstu_time_features)"""
+    L.require_gpu_tensor(timestamps, "timestamps")
+    t = timestamps.reshape(-1).to(torch.int64).contiguous()
+    pu, upp = _periods(period_units, units_per_period, t.device)
+    out = torch.empty((t.numel(), 2 * pu.numel()), dtype=torch.float32, device=t.device)
+    with torch.cuda.device(t.device):
+        L.check(L.lib().hstu_time_features(t.data_ptr(), pu.data_ptr(), upp.data_ptr(), pu.numel(), out.data_ptr(), t.numel(),
+                                           L.current_stream_ptr(t.device)))
+    return out
+
+
+def time_ln_fwd(z0, timestamps, period_units, units_per_period, b, wt, ln_weight, ln_bias, eps):
+    """y = LayerNorm(z0 + b + tf(timestamps) @ wt) ln_weight + ln_bias in one row pass: returns (y, mean, rstd).  ``wt``
+    (2F, dim), ``b``, ``ln_weight``, ``ln_bias`` are fp32."""
+    L.require_gpu_tensor(z0, "z0")
+    z0 = z0.contiguous()
+    rows, dim = z0.shape
+    t = timestamps.reshape(-1).to(torch.int64).contiguous()
+    torch._assert(t.numel() == rows, "one timestamp per row")
+    pu, upp = _periods(period_units, units_per_period, z0.device)
+    b, wt, g, h = _f32c(b), _f32c(wt), _f32c(ln_weight), _f32c(ln_bias)
+    torch._assert(wt.shape == (2 * pu.numel(), dim), "wt must be (2F, dim)")
+    y = torch.empty_like(z0)
+    mean, rstd = _f32(rows, z0.device), _f32(rows, z0.device)
+    with torch.cuda.device(z0.device):
+        L.check(L.lib().hstu_time_ln_fwd(z0.data_ptr(), t.data_ptr(), pu.data_ptr(), upp.data_ptr(), pu.numel(), b.data_ptr(),
+                                         wt.data_ptr(), g.data_ptr(), h.data_ptr(), float(eps), y.data_ptr(), mean.data_ptr(),
+                                         rstd.data_ptr(), rows, dim, L.torch_dtype_code(z0.dtype), L.current_stream_ptr(z0.device)))
+    return y, mean, rstd
+
+
+def time_ln_bwd(dy, z0, timestamps, period_units, units_per_period, b, wt, ln_weight, mean, rstd):
+    """dz (z0's dtype) and the fp32 column sums dln_weight, dln_bias, db (dim), dwt (2F, dim) of time_ln_fwd"""
+    dy, z0 = dy.contiguous(), z0.contiguous()
+    rows, dim = z0.shape
+    dev = z0.device
+    t = timestamps.reshape(-1).to(torch.int64).contiguous()
+    pu, upp = _periods(period_units, units_per_period, dev)
+    b, wt, g = _f32c(b), _f32c(wt), _f32c(ln_weight)
+    dz = torch.empty_like(z0)
+    dg, dh, db = _f32(dim, dev), _f32(dim, dev), _f32(dim, dev)
+    dwt = torch.empty((2 * pu.numel(), dim), dtype=torch.float32, device=dev)
+    ws = torch.empty(L.lib().hstu_time_ln_workspace_bytes(dim, pu.numel()), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().hstu_time_ln_bwd(dy.data_ptr(), z0.data_ptr(), t.data_ptr(), pu.data_ptr(), upp.data_ptr(), pu.numel(),
+                                         b.data_ptr(), wt.data_ptr(), g.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dz.data_ptr(),
+                                         dg.data_ptr(), dh.data_ptr(), db.data_ptr(), dwt.data_ptr(), ws.data_ptr(), rows, dim,
+                                         L.torch_dtype_code(z0.dtype), L.current_stream_ptr(dev)))
+    return dz, dg, dh, db, dwt

@@ -594,6 +594,43 @@ int hstu_combine_embeddings_bwd(const void* d_out, const void* seq_offsets, cons
                                 int64_t total_targets, int32_t batch, int32_t contextual_len, int32_t dim, int mode, int dtype,
                                 int index_dtype, void* stream);
 
+/* ---- TimestampLayerNormPostprocessor behind its GEMM: time features + rank-2F update + bias + LayerNorm in one row pass ----
+ * The postprocessor DlrmHSTU builds (modules/dlrm_hstu.py:182-191, modules/postprocessors.py:105-176) concatenates 2F time
+ * features onto every D-wide row, runs Linear(D + 2F, D) and a LayerNorm.  With the combiner weight split W = [Wx | Wt] the
+ * GEMM is the aligned z0 = x Wx^T (hstu_linear_k512 at D = 512) and the rest is one row pass over z0.
+ * Time features (postprocessors.py:133-165, the reference's fp32 arithmetic, NOT integer arithmetic): for period p
+ *   a = (float)t;  units = torch.div(a, period_units[p], rounding_mode="floor")   (fmod-based, IEEE divides)
+ *   angle = ((torch.remainder(units, units_per_period[p]) / units_per_period[p]) * 2) * 3.14
+ *   features [2p, 2p + 1] = [cos(angle), sin(angle)]
+ * period_units, units_per_period: (num_periods) fp32 DEVICE arrays (the module's buffers).  1 <= num_periods <= 4 for the
+ * fused row pass; hstu_time_features alone (the unfused composition, any module) takes up to 1024.
+ * hstu_time_features writes out (rows, 2 num_periods) fp32 contiguous; timestamps (rows) int64.  rows == 0: no launch. */
+#define HSTU_TIME_LN_MAX_PERIODS 4
+#define HSTU_TIME_FEATURES_MAX_PERIODS 1024
+#define HSTU_TIME_LN_MAX_BLOCKS 1024        /* grid cap of the row kernels (they loop over rows beyond it) */
+int hstu_time_features(const int64_t* timestamps, const float* period_units, const float* units_per_period, int32_t num_periods,
+                       float* out, int64_t rows, void* stream);
+/* Per row l of z0 (rows, dim; contiguous, `dtype`: the GEMM's output), fp32 math throughout:
+ *   z = z0 + b + sum_j tf_j(timestamps[l]) wt[j, :]          (never written to memory)
+ *   y = (z - mean) rstd ln_weight + ln_bias                   y (rows, dim) contiguous in `dtype`
+ * b, ln_weight, ln_bias (dim) and wt (2 num_periods, dim; the transposed time columns of W) are fp32 contiguous; mean, rstd
+ * (rows) fp32, may be NULL.  Rows are read in 16-byte pieces when dim and every pointer allow it, element by element
+ * otherwise; dim <= 4096 (pieces) / 2048 (elements), as hstu_layer_norm_fwd.  rows == 0 launches nothing. */
+int hstu_time_ln_fwd(const void* z0, const int64_t* timestamps, const float* period_units, const float* units_per_period,
+                     int32_t num_periods, const float* b, const float* wt, const float* ln_weight, const float* ln_bias, float eps,
+                     void* y, float* mean, float* rstd, int64_t rows, int32_t dim, int dtype, void* stream);
+/* z is recomputed from z0 and the timestamps; with xhat = (z - mean) rstd and g = dy ln_weight
+ *   dz = rstd (g - mean_c(g) - xhat mean_c(g xhat))          dz (rows, dim) in `dtype`: feeds the two GEMM gradients
+ *   dln_weight = sum_l dy xhat, dln_bias = sum_l dy, db = sum_l dz (dim), dwt[j] = sum_l tf_j dz (2 num_periods, dim): fp32
+ * The 3 + 2 num_periods column sums run in a fixed order (per-workgroup partials in `workspace`, then a finish kernel): no
+ * float atomics, bit-identical run to run.  `workspace`: hstu_time_ln_workspace_bytes(dim, num_periods) bytes of device
+ * memory, 16-byte aligned, independent of rows.  rows == 0 zeroes the four reduced outputs and launches nothing. */
+size_t hstu_time_ln_workspace_bytes(int32_t dim, int32_t num_periods);
+int hstu_time_ln_bwd(const void* dy, const void* z0, const int64_t* timestamps, const float* period_units,
+                     const float* units_per_period, int32_t num_periods, const float* b, const float* wt, const float* ln_weight,
+                     const float* mean, const float* rstd, void* dz, float* dln_weight, float* dln_bias, float* db, float* dwt,
+                     void* workspace, int64_t rows, int32_t dim, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
