@@ -161,6 +161,11 @@ SIGNATURES = {
     "hstu_time_ln_fwd": (_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _i32, _int, _vp]),
     "hstu_time_ln_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32,
                                 _int, _vp]),
+    "hstu_softmax_attn_supported": (_int, [_int, _i32, _i32]),
+    "hstu_softmax_attn_fwd": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32,
+                                     _f32, _f32, C.c_uint64, _int, _int, _vp]),
+    "hstu_softmax_attn_bwd": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                     _i32, _i32, _i32, _i32, _f32, _f32, C.c_uint64, _int, _int, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -355,4 +355,78 @@ int hstu_multitask_head_bwd(const float* grad_loss, const float* grad_pred, cons
                                    num_binary, loss_scale, dtype, vec, (hipStream_t)stream);
 }
 
+// ---- jagged causal softmax attention ----------------------------------------------------------------------------------------
+// checks that need no pointer first (shape, type codes, ranges), then pointers, then alignment
+static int validate_softmax_attn(const char* who, const SoftmaxAttnArgs& a, int64_t total_rows, bool backward, bool* empty) {
+  if (a.dtype != HSTU_DTYPE_BF16 && a.dtype != HSTU_DTYPE_F16 && a.dtype != HSTU_DTYPE_F32)
+    return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32 (got code %d)", who, a.dtype);
+  if (a.index_dtype != HSTU_INDEX_I32 && a.index_dtype != HSTU_INDEX_I64)
+    return set_error(HSTU_EINVAL, "%s: seq_offsets must be int32 or int64 (got code %d)", who, a.index_dtype);
+  if (a.batch < 0 || total_rows < 0 || a.heads <= 0) return set_error(HSTU_EINVAL, "%s: bad batch / total_rows / heads", who);
+  if (a.head_dim <= 0) return set_error(HSTU_EINVAL, "%s: head_dim must be positive (got %d)", who, a.head_dim);
+  if (a.head_dim > HSTU_SOFTMAX_ATTN_MAX_HEAD_DIM)
+    return set_error(HSTU_EUNSUPPORTED, "%s: head_dim %d exceeds the limit of %d", who, a.head_dim, HSTU_SOFTMAX_ATTN_MAX_HEAD_DIM);
+  const int eb = a.dtype == HSTU_DTYPE_F32 ? 4 : 2, epu = 16 / eb;
+  if (a.head_dim % epu)
+    return set_error(HSTU_EINVAL, "%s: head_dim (%d) must be a multiple of %d elements (16 bytes); zero-pad it", who, a.head_dim, epu);
+  if (a.max_seq_len < 1) return set_error(HSTU_EINVAL, "%s: max_seq_len must be at least 1 (got %d)", who, a.max_seq_len);
+  if (a.max_seq_len > HSTU_SOFTMAX_ATTN_MAX_SEQ_LEN)
+    return set_error(HSTU_EUNSUPPORTED, "%s: max_seq_len %d exceeds the limit of %d", who, a.max_seq_len, HSTU_SOFTMAX_ATTN_MAX_SEQ_LEN);
+  if (!(a.dropout_p >= 0.f && a.dropout_p < 1.f)) return set_error(HSTU_EINVAL, "%s: dropout_p must be in [0, 1) (got %g)", who, (double)a.dropout_p);
+  if (!(a.scale == a.scale)) return set_error(HSTU_EINVAL, "%s: scale is NaN", who);
+  *empty = a.batch == 0 || total_rows == 0;
+  if (*empty) return HSTU_OK;
+  if (!a.q || !a.k || !a.v || !a.out || !a.lse || !a.offsets)
+    return set_error(HSTU_EINVAL, "%s: q, k, v, out, lse and seq_offsets must be non-NULL", who);
+  if (backward && (!a.dout || !a.delta || !a.dq || !a.dk || !a.dv))
+    return set_error(HSTU_EINVAL, "%s: dout, delta, dq, dk and dv must be non-NULL", who);
+  const int64_t strides[] = {a.q_rs, a.q_hs, a.k_rs, a.k_hs, a.v_rs, a.v_hs};
+  for (int64_t s : strides)
+    if ((s * eb) % 16) return set_error(HSTU_EINVAL, "%s: every (row, head) vector must be 16-byte aligned (stride %lld elements)", who, (long long)s);
+  if (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.out | (uintptr_t)a.dout | (uintptr_t)a.dq | (uintptr_t)a.dk |
+       (uintptr_t)a.dv) & 15)
+    return set_error(HSTU_EINVAL, "%s: tensor base pointers must be 16-byte aligned", who);
+  if (((uintptr_t)a.lse | (uintptr_t)a.delta) & 3) return set_error(HSTU_EINVAL, "%s: lse / delta must be 4-byte aligned", who);
+  return HSTU_OK;
+}
+
+int hstu_softmax_attn_supported(int dtype, int32_t head_dim, int32_t max_seq_len) {
+  if (dtype != HSTU_DTYPE_BF16 && dtype != HSTU_DTYPE_F16 && dtype != HSTU_DTYPE_F32) return 0;
+  return head_dim >= 1 && head_dim <= HSTU_SOFTMAX_ATTN_MAX_HEAD_DIM && max_seq_len >= 1 && max_seq_len <= HSTU_SOFTMAX_ATTN_MAX_SEQ_LEN;
+}
+
+int hstu_softmax_attn_fwd(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k, int64_t k_row_stride,
+                          int64_t k_head_stride, const void* v, int64_t v_row_stride, int64_t v_head_stride, void* out, float* lse,
+                          const void* seq_offsets, int64_t total_rows, int32_t batch, int32_t heads, int32_t head_dim,
+                          int32_t max_seq_len, float scale, float dropout_p, uint64_t seed, int dtype, int index_dtype,
+                          void* stream) {
+  SoftmaxAttnArgs a{};
+  a.q = q; a.k = k; a.v = v;
+  a.q_rs = q_row_stride; a.q_hs = q_head_stride; a.k_rs = k_row_stride; a.k_hs = k_head_stride; a.v_rs = v_row_stride; a.v_hs = v_head_stride;
+  a.out = out; a.lse = lse; a.offsets = seq_offsets;
+  a.batch = batch; a.heads = heads; a.head_dim = head_dim; a.max_seq_len = max_seq_len;
+  a.scale = scale; a.dropout_p = dropout_p; a.seed = seed; a.dtype = dtype; a.index_dtype = index_dtype;
+  bool empty = false;
+  if (int e = validate_softmax_attn("hstu_softmax_attn_fwd", a, total_rows, false, &empty)) return e;
+  if (empty) return HSTU_OK;
+  return launch_softmax_attn_fwd(a, (hipStream_t)stream);
+}
+
+int hstu_softmax_attn_bwd(const void* dout, const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k,
+                          int64_t k_row_stride, int64_t k_head_stride, const void* v, int64_t v_row_stride, int64_t v_head_stride,
+                          const void* out, const float* lse, float* delta, void* dq, void* dk, void* dv, const void* seq_offsets,
+                          int64_t total_rows, int32_t batch, int32_t heads, int32_t head_dim, int32_t max_seq_len, float scale,
+                          float dropout_p, uint64_t seed, int dtype, int index_dtype, void* stream) {
+  SoftmaxAttnArgs a{};
+  a.q = q; a.k = k; a.v = v;
+  a.q_rs = q_row_stride; a.q_hs = q_head_stride; a.k_rs = k_row_stride; a.k_hs = k_head_stride; a.v_rs = v_row_stride; a.v_hs = v_head_stride;
+  a.out = out; a.lse = lse; a.dout = dout; a.delta = delta; a.dq = dq; a.dk = dk; a.dv = dv; a.offsets = seq_offsets;
+  a.batch = batch; a.heads = heads; a.head_dim = head_dim; a.max_seq_len = max_seq_len;
+  a.scale = scale; a.dropout_p = dropout_p; a.seed = seed; a.dtype = dtype; a.index_dtype = index_dtype;
+  bool empty = false;
+  if (int e = validate_softmax_attn("hstu_softmax_attn_bwd", a, total_rows, true, &empty)) return e;
+  if (empty) return HSTU_OK;
+  return launch_softmax_attn_bwd(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

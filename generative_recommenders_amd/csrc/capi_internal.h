@@ -129,4 +129,24 @@ int launch_multitask_head_bwd(const float* grad_loss, const float* grad_pred, co
                               const float* mean, const float* rstd, const float* weight_sum, void* dx, int64_t dx_rs, float* dw,
                               float* dc, float* dln_w, float* dln_b, void* workspace, int64_t rows, int dim, int tasks, int nbin,
                               float loss_scale, int dtype, bool vec, hipStream_t st);
+
+// jagged causal softmax attention (softmax_attn.hip): arguments as validated by capi.hip.  Instantiated at head dims 32 and
+// 64 (smaller ones are zero-filled on load); one wavefront per (user, head, 32-row tile).
+struct SoftmaxAttnArgs {
+  const void *q, *k, *v;
+  int64_t q_rs, q_hs, k_rs, k_hs, v_rs, v_hs;
+  const void* out;         // forward: written
+  const float* lse;        // forward: written
+  const void* dout;        // backward only from here
+  float* delta;
+  void *dq, *dk, *dv;
+  const void* offsets;
+  int batch, heads, head_dim, max_seq_len;
+  float scale, dropout_p;
+  uint64_t seed;
+  int dtype, index_dtype;
+};
+inline int softmax_attn_head_dim(int d) { return d <= 0 ? 0 : (d <= 32 ? 32 : (d <= HSTU_SOFTMAX_ATTN_MAX_HEAD_DIM ? 64 : 0)); }
+int launch_softmax_attn_fwd(const SoftmaxAttnArgs& a, hipStream_t st);
+int launch_softmax_attn_bwd(const SoftmaxAttnArgs& a, hipStream_t st);
 }  // namespace hstu

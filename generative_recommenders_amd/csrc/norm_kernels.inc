@@ -92,18 +92,7 @@ struct DropCtx {
   float scale;
   uint32_t s0, s1;
 };
-HSTU_DEV uint32_t drop_key(uint32_t hi, uint32_t s0, uint32_t s1) {
-  const uint32_t k = s1 + hi * 0x9e3779b9u;
-  return s0 ^ ((k << 16) | (k >> 16));
-}
-HSTU_DEV uint32_t drop_hash(uint32_t lo, uint32_t key, uint32_t s0, uint32_t s1) {
-  // (both seed words enter once more BEHIND the first multiply, as a wave-uniform addend: with the seed only XORed into the index, the masks of two
-  // seeds were index-XOR permutations of one table -- mask_B[i] = mask_A[i ^ d] -- and seeds with equal keys gave equal masks;
-  // one add per element pair, no multiply: round 5's advisor)
-  uint32_t h = lo ^ key;
-  h ^= h >> 16; h *= 0x85ebca6bu; h += s1 ^ ((s0 << 13) | (s0 >> 19)); h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  return h;
-}
+// drop_key / drop_hash: drop_hash.cuh (shared with the softmax attention)
 // v[i] *= keep(e0 + i) ? scale : 0 for i < VEC; e0 = index of v[0] in the output tensor, a multiple of VEC (rows, column
 // offsets and the output stride of a vector instantiation are multiples of VEC): the VEC / 2 pair indices of a piece then
 // share their high word -- pe0 is a multiple of VEC / 2 -- and the key is formed once per piece
@@ -129,9 +118,8 @@ HSTU_DEV void drop_apply(RowVec<T, VEC>& r, int64_t e0, const DropCtx& dc) {
 }
 static DropCtx make_drop_ctx(float ratio, uint64_t seed) {
   DropCtx dc;
-  double t = (double)ratio * 65536.0 + 0.5;
-  dc.thr = ratio > 0.f ? (uint32_t)(t < 1.0 ? 1.0 : (t > 65535.0 ? 65535.0 : t)) : 0u;
-  dc.scale = 65536.0f / (float)(65536u - dc.thr);
+  dc.thr = drop_threshold(ratio);
+  dc.scale = drop_scale(dc.thr);
   dc.s0 = (uint32_t)seed;
   dc.s1 = (uint32_t)(seed >> 32);
   return dc;

@@ -10,6 +10,7 @@
 // kernels replaced: ops/triton/triton_layer_norm.py:77-309,
 // ops/triton/triton_hstu_linear.py:48-337 (LN * u), :570-1036 (GroupNorm * u).
 #include "hstu_common.cuh"
+#include "drop_hash.cuh"
 #include "capi_internal.h"
 #include "norm_dispatch.h"
 

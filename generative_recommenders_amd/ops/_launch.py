@@ -1224,3 +1224,68 @@ def time_ln_bwd(dy, z0, timestamps, period_units, units_per_period, b, wt, ln_we
                                          dg.data_ptr(), dh.data_ptr(), db.data_ptr(), dwt.data_ptr(), ws.data_ptr(), rows, dim,
                                          L.torch_dtype_code(z0.dtype), L.current_stream_ptr(dev)))
     return dz, dg, dh, db, dwt
+
+
+# ------------------------------------------------------------------ jagged causal softmax attention (the SASRec baseline)
+SOFTMAX_ATTN_MAX_HEAD_DIM = 64
+SOFTMAX_ATTN_MAX_SEQ_LEN = 512
+
+
+def softmax_attn_supported(dtype: torch.dtype, head_dim: int, max_seq_len: int) -> bool:
+    """whether the fused kernels take this (dtype, REAL head dim, max_seq_len): hstu_softmax_attn_supported"""
+    if dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        return False
+    return 1 <= int(head_dim) <= SOFTMAX_ATTN_MAX_HEAD_DIM and 1 <= int(max_seq_len) <= SOFTMAX_ATTN_MAX_SEQ_LEN
+
+
+def _softmax_attn_check(q, k, v, seq_offsets):
+    for name, t in (("q", q), ("k", k), ("v", v), ("seq_offsets", seq_offsets)):
+        L.require_gpu_tensor(t, name)
+    if not (q.dtype == k.dtype == v.dtype):
+        raise RuntimeError("q, k, v must have the same dtype")
+    if not (q.dim() == 3 and q.shape == k.shape == v.shape):
+        raise RuntimeError(f"q, k, v must be (L, H, d) with one head dim, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+
+
+def softmax_attn_fwd(q, k, v, seq_offsets, max_seq_len, scale, dropout_p=0.0, seed=0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(out (L, H, d), lse (L, H) fp32) of the jagged causal softmax attention; q, k, v (L, H, d) with d a multiple of 16
+    bytes, any row / head strides (hstu_softmax_attn_fwd).  ``lse`` is taken of the un-dropped scores."""
+    _softmax_attn_check(q, k, v, seq_offsets)
+    q, k, v = _aligned_rows(q), _aligned_rows(k), _aligned_rows(v)
+    seq_offsets = _idx(seq_offsets)
+    rows, heads, d = q.shape
+    out = torch.empty((rows, heads, d), dtype=q.dtype, device=q.device)
+    lse = torch.empty((rows, heads), dtype=torch.float32, device=q.device)
+    if rows == 0 or seq_offsets.numel() < 2:
+        return out, lse
+    if DEBUG_CHECKS:
+        _check_attention_metadata(q, seq_offsets, max_seq_len, 0)
+    with torch.cuda.device(q.device):
+        L.check(L.lib().hstu_softmax_attn_fwd(
+            q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(), v.stride(0), v.stride(1),
+            out.data_ptr(), lse.data_ptr(), seq_offsets.data_ptr(), rows, seq_offsets.numel() - 1, heads, d, int(max_seq_len),
+            float(scale), float(dropout_p), int(seed), L.torch_dtype_code(q.dtype), L.index_dtype_code(seq_offsets),
+            L.current_stream_ptr(q.device)))
+    return out, lse
+
+
+def softmax_attn_bwd(dout, q, k, v, out, lse, seq_offsets, max_seq_len, scale, dropout_p=0.0, seed=0):
+    """(dq, dk, dv), contiguous (L, H, d), of softmax_attn_fwd; P is recomputed from q, k and ``lse`` and the dropout mask
+    from ``seed``.  No float atomics: bit-identical run to run (hstu_softmax_attn_bwd)."""
+    _softmax_attn_check(q, k, v, seq_offsets)
+    q, k, v = _aligned_rows(q), _aligned_rows(k), _aligned_rows(v)
+    seq_offsets = _idx(seq_offsets)
+    dout, out, lse = dout.contiguous(), out.contiguous(), lse.contiguous()
+    rows, heads, d = q.shape
+    dq, dk, dv = (torch.empty((rows, heads, d), dtype=q.dtype, device=q.device) for _ in range(3))
+    if rows == 0 or seq_offsets.numel() < 2:
+        return dq, dk, dv
+    delta = torch.empty((rows, heads), dtype=torch.float32, device=q.device)
+    with torch.cuda.device(q.device):
+        L.check(L.lib().hstu_softmax_attn_bwd(
+            dout.data_ptr(), q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(),
+            v.stride(0), v.stride(1), out.data_ptr(), lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+            dv.data_ptr(), seq_offsets.data_ptr(), rows, seq_offsets.numel() - 1, heads, d, int(max_seq_len), float(scale),
+            float(dropout_p), int(seed), L.torch_dtype_code(q.dtype), L.index_dtype_code(seq_offsets),
+            L.current_stream_ptr(q.device)))
+    return dq, dk, dv

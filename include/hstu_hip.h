@@ -631,6 +631,36 @@ int hstu_time_ln_bwd(const void* dy, const void* z0, const int64_t* timestamps, 
                      const float* mean, const float* rstd, void* dz, float* dln_weight, float* dln_bias, float* db, float* dwt,
                      void* workspace, int64_t rows, int32_t dim, int dtype, void* stream);
 
+/* ---- jagged causal softmax attention (the SASRec baseline's attention) -----------------------------------------------------
+ * What research/modeling/sequential/sasrec.py:209-214 runs through torch.nn.MultiheadAttention on a padded (B, N, D) batch
+ * with an (N, N) mask, on jagged rows: row i of user b sees rows j <= i of user b,
+ *   S[i,j] = scale <q_i, k_j>,  P = softmax_j(S),  O = dropout_p(P) V,  lse[i] = ln sum_j exp(S[i,j])   (un-dropped scores)
+ * No (N, N) object exists in memory.  q, k, v: (total_rows, heads, head_dim) in `dtype` with row / head strides in ELEMENTS
+ * (k and v may be column slices of one GEMM output); every (row, head) vector 16-byte aligned, so head_dim is a multiple
+ * of 16 bytes (zero-pad it; `scale` is the caller's, usually real_head_dim^-0.5).  out, dout, dq, dk, dv are contiguous
+ * (total_rows, heads, head_dim) in `dtype`; lse and delta are contiguous (total_rows, heads) fp32.  Users longer than
+ * max_seq_len are a caller error (their rows past it are not written).
+ * Fused range (hstu_softmax_attn_supported returns 1): bf16 / fp16 / fp32, 1 <= head_dim <= 64, 1 <= max_seq_len <= 512.
+ * Dropout: 0 <= dropout_p < 1; element (row r, head h, key position j inside its user) has the index
+ * e = (r heads + h) max_seq_len + j of the generator of hstu_norm_mul_dropout_fwd (same threshold, survivor scale and pair
+ * rule); the backward regenerates the mask from `seed`.  batch == 0 or total_rows == 0 launches nothing. */
+#define HSTU_SOFTMAX_ATTN_MAX_HEAD_DIM 64
+#define HSTU_SOFTMAX_ATTN_MAX_SEQ_LEN 512
+int hstu_softmax_attn_supported(int dtype, int32_t head_dim, int32_t max_seq_len);
+int hstu_softmax_attn_fwd(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k, int64_t k_row_stride,
+                          int64_t k_head_stride, const void* v, int64_t v_row_stride, int64_t v_head_stride, void* out, float* lse,
+                          const void* seq_offsets, int64_t total_rows, int32_t batch, int32_t heads, int32_t head_dim,
+                          int32_t max_seq_len, float scale, float dropout_p, uint64_t seed, int dtype, int index_dtype,
+                          void* stream);
+/* P is recomputed from q, k and lse; delta = rowsum(dout * out) is written to `delta` (scratch of the call) by the dQ kernel
+ * and read by the dK / dV kernel; dS = P (dP - delta).  Every dq / dk / dv row is owned by one wavefront: no float atomics,
+ * bit-identical run to run. */
+int hstu_softmax_attn_bwd(const void* dout, const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k,
+                          int64_t k_row_stride, int64_t k_head_stride, const void* v, int64_t v_row_stride, int64_t v_head_stride,
+                          const void* out, const float* lse, float* delta, void* dq, void* dk, void* dv, const void* seq_offsets,
+                          int64_t total_rows, int32_t batch, int32_t heads, int32_t head_dim, int32_t max_seq_len, float scale,
+                          float dropout_p, uint64_t seed, int dtype, int index_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
