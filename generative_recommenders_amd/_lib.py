@@ -166,6 +166,11 @@ SIGNATURES = {
                                      _f32, _f32, C.c_uint64, _int, _int, _vp]),
     "hstu_softmax_attn_bwd": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                      _i32, _i32, _i32, _i32, _f32, _f32, C.c_uint64, _int, _int, _vp]),
+    "hstu_input_preprocess_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _int, _f32,
+                                         C.c_uint64, _int, _int, _int, _vp]),
+    "hstu_input_preprocess_bwd_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, _i32, _int]),
+    "hstu_input_preprocess_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _int, _f32,
+                                         C.c_uint64, _int, _int, _int, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

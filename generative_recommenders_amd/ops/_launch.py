@@ -1153,6 +1153,112 @@ def combine_embeddings_bwd(d_out, seq_offsets, num_targets, out_offsets, mode: i
     return d_content, d_action, d_ctx
 
 
+# ---- research-path input preprocessors (hstu_input_preprocess_*) ------------------------------------------------------
+PREPROCESS_PLAIN, PREPROCESS_CONCAT, PREPROCESS_INTERLEAVE = 0, 1, 2     # HSTU_PREPROCESS_*
+PREPROCESS_MAX_DIM = 4096        # HSTU_PREPROCESS_MAX_DIM
+
+
+def input_preprocess_dims(layout: int, past_ids, past_embeddings, ratings, pos_table, rating_table):
+    """(B, N, N', Di, Dr, Do, P, R) of a call, or RuntimeError -- from the shapes alone, before any tensor is touched"""
+    if layout not in (PREPROCESS_PLAIN, PREPROCESS_CONCAT, PREPROCESS_INTERLEAVE):
+        raise RuntimeError(f"input_preprocess: unknown layout {layout}")
+    if past_ids.dim() != 2 or past_embeddings.dim() != 3 or tuple(past_embeddings.shape[:2]) != tuple(past_ids.shape):
+        raise RuntimeError(f"input_preprocess: past_ids (B, N) and past_embeddings (B, N, Di) expected, got "
+                           f"{tuple(past_ids.shape)} and {tuple(past_embeddings.shape)}")
+    if pos_table.dim() != 2:
+        raise RuntimeError(f"input_preprocess: the position table is (P, Do), got {tuple(pos_table.shape)}")
+    B, N, Di = past_embeddings.shape
+    P = pos_table.shape[0]
+    Dr = R = 0
+    if layout != PREPROCESS_PLAIN:
+        if ratings is None or rating_table is None:
+            raise RuntimeError("input_preprocess: the rated layouts need ratings and the rating table")
+        if tuple(ratings.shape) != (B, N) or rating_table.dim() != 2:
+            raise RuntimeError(f"input_preprocess: ratings (B, N) and a rating table (R, Dr) expected, got "
+                               f"{tuple(ratings.shape)} and {tuple(rating_table.shape)}")
+        R, Dr = rating_table.shape
+        if layout == PREPROCESS_INTERLEAVE and Dr != Di:
+            raise RuntimeError(f"input_preprocess: interleaving needs rating rows as wide as the item rows, got {Dr} and {Di}")
+    Do = Di + Dr if layout == PREPROCESS_CONCAT else Di
+    n_out = 2 * N if layout == PREPROCESS_INTERLEAVE else N
+    if pos_table.shape[1] != Do:
+        raise RuntimeError(f"input_preprocess: the position table has {pos_table.shape[1]} columns, the output rows {Do}")
+    if n_out > P:
+        raise RuntimeError(f"input_preprocess: {n_out} output positions but the position table has {P} rows")
+    if Do > PREPROCESS_MAX_DIM:
+        raise RuntimeError(f"input_preprocess: rows of at most {PREPROCESS_MAX_DIM} columns, got {Do}")
+    if B * n_out > MAX_ROWS:
+        raise RuntimeError(f"input_preprocess: {B} x {n_out} output rows: at most 2^31 - 1 are supported")
+    return B, N, n_out, Di, Dr, Do, P, R
+
+
+def _preprocess_ints(past_ids, ratings):
+    if past_ids.dtype != torch.int64:
+        past_ids = past_ids.to(torch.int64)
+    return past_ids.contiguous(), (None if ratings is None else _idx(ratings))
+
+
+def input_preprocess_fwd(layout: int, past_ids, past_embeddings, ratings, pos_table, rating_table, dropout_ratio: float,
+                         seed: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(out (B, N', Do) in result_type(past_embeddings, pos_table), valid_mask (B, N', 1) fp32)"""
+    B, N, n_out, Di, Dr, Do, P, R = input_preprocess_dims(layout, past_ids, past_embeddings, ratings, pos_table, rating_table)
+    for t, name in ((past_embeddings, "past_embeddings"), (past_ids, "past_ids"), (pos_table, "pos_table")):
+        L.require_gpu_tensor(t, name)
+    if layout != PREPROCESS_PLAIN:
+        L.require_gpu_tensor(ratings, "ratings")
+        L.require_gpu_tensor(rating_table, "rating_table")
+    dev = past_embeddings.device
+    out_dtype = torch.result_type(past_embeddings, pos_table)
+    emb = past_embeddings.contiguous()
+    if emb.dtype != out_dtype and out_dtype != torch.float32:       # bf16 against fp16: torch promotes both to fp32
+        raise RuntimeError(f"input_preprocess: {emb.dtype} embeddings into a {pos_table.dtype} table")
+    pos = pos_table.detach().to(out_dtype).contiguous()
+    rat = None if layout == PREPROCESS_PLAIN else rating_table.detach().to(out_dtype).contiguous()
+    ids, rt = _preprocess_ints(past_ids, ratings if layout != PREPROCESS_PLAIN else None)
+    out = torch.empty((B, n_out, Do), dtype=out_dtype, device=dev)
+    valid = torch.empty((B, n_out, 1), dtype=torch.float32, device=dev)
+    if B == 0 or N == 0:
+        return out, valid
+    with torch.cuda.device(dev):
+        L.check(L.lib().hstu_input_preprocess_fwd(ids.data_ptr(), emb.data_ptr(), _vp(rt), pos.data_ptr(), _vp(rat), out.data_ptr(),
+                                                  valid.data_ptr(), B, N, Di, Dr, P, R, layout, float(dropout_ratio), int(seed),
+                                                  L.torch_dtype_code(emb.dtype), L.torch_dtype_code(out_dtype),
+                                                  L.index_dtype_code(rt) if rt is not None else L.HSTU_INDEX_I64,
+                                                  L.current_stream_ptr(dev)))
+    return out, valid
+
+
+def input_preprocess_bwd(layout: int, d_out, past_ids, ratings, emb_dtype: torch.dtype, item_dim: int, num_positions: int,
+                         rating_shape: Optional[Tuple[int, int]], dropout_ratio: float, seed: int, need_emb: bool = True,
+                         need_pos: bool = True, need_rating: bool = True):
+    """(d_past_embeddings in `emb_dtype`, d_pos (P, Do) fp32, d_rating (R, Dr) fp32); what is not needed is None.  The table
+    gradients are fp32 sums in a fixed order."""
+    L.require_gpu_tensor(d_out, "d_out")
+    dev = d_out.device
+    d_out = d_out.contiguous()
+    B, N = past_ids.shape
+    Do = d_out.shape[-1]
+    R, Dr = rating_shape if layout != PREPROCESS_PLAIN else (0, 0)
+    need_rating = need_rating and layout != PREPROCESS_PLAIN
+    ids, rt = _preprocess_ints(past_ids, ratings if layout != PREPROCESS_PLAIN else None)
+    if not (need_emb or need_pos or need_rating):
+        return None, None, None
+    d_emb = torch.empty((B, N, item_dim), dtype=emb_dtype, device=dev) if need_emb else None
+    d_pos = torch.empty((num_positions, Do), dtype=torch.float32, device=dev) if need_pos else None
+    d_rat = torch.empty((R, Dr), dtype=torch.float32, device=dev) if need_rating else None
+    ws = None
+    if need_pos or need_rating:
+        ws = torch.empty(max(32, L.lib().hstu_input_preprocess_bwd_workspace_bytes(B, N, item_dim, Dr, R, layout)),
+                         dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().hstu_input_preprocess_bwd(d_out.data_ptr(), ids.data_ptr(), _vp(rt), _vp(d_emb), _vp(d_pos), _vp(d_rat),
+                                                  _vp(ws), B, N, item_dim, Dr, num_positions, R, layout, float(dropout_ratio),
+                                                  int(seed), L.torch_dtype_code(emb_dtype), L.torch_dtype_code(d_out.dtype),
+                                                  L.index_dtype_code(rt) if rt is not None else L.HSTU_INDEX_I64,
+                                                  L.current_stream_ptr(dev)))
+    return d_emb, d_pos, d_rat
+
+
 # ---- timestamp postprocessor (hstu_time_features / hstu_time_ln_*) ---------------------------------------------------
 TIME_LN_MAX_PERIODS = 4          # HSTU_TIME_LN_MAX_PERIODS
 

@@ -661,6 +661,47 @@ int hstu_softmax_attn_bwd(const void* dout, const void* q, int64_t q_row_stride,
                           int64_t total_rows, int32_t batch, int32_t heads, int32_t head_dim, int32_t max_seq_len, float scale,
                           float dropout_p, uint64_t seed, int dtype, int index_dtype, void* stream);
 
+/* The input-feature preprocessors of the research path (research/modeling/sequential/input_features_preprocessors.py) as
+ * one row pass.  past_ids (batch, n) int64, past_embeddings (batch, n, item_dim) in `emb_dtype`, ratings (batch, n) int32 /
+ * int64 (`rating_index_dtype`; rated layouts only), pos_table (num_positions, Do) and rating_table (num_ratings, rating_dim)
+ * in `out_dtype`.  With s = fl32(Do ** 0.5) and m(b, i) = past_ids[b, i] != 0 (by id, not by length):
+ *   out[b, n', c] = m * drop(src(b, n', c) * s + pos_table[n', c]),  valid_mask[b, n'] = m  (fp32 whatever the dtypes)
+ *   HSTU_PREPROCESS_PLAIN       Do = item_dim, N' = n: src = past_embeddings[b, n', c]                     (:72-89)
+ *   HSTU_PREPROCESS_CONCAT      Do = item_dim + rating_dim, N' = n: columns >= item_dim are
+ *                               rating_table[ratings[b, n'], c - item_dim]                                 (:133-152)
+ *   HSTU_PREPROCESS_INTERLEAVE  rating_dim == item_dim == Do, N' = 2 n: row 2 i is the item, row 2 i + 1 is
+ *                               rating_table[ratings[b, i], :], both masked by m(b, i)                     (:226-260)
+ * fp32: fl(src s), fl(. + pos), [fl(. scale) under dropout], fl(. m) are separate roundings -- bit-exact against the
+ * reference with dropout off; 16-bit: fp32 arithmetic, one rounding at the store.  `out_dtype` is `emb_dtype`, or fp32 for
+ * 16-bit embeddings (torch.result_type of a 16-bit activation and an fp32 module).  Dropout: the generator of
+ * hstu_norm_mul_dropout_fwd with element index e = (b N' + n') Do + c (same threshold, survivor scale and pair rule);
+ * nothing is stored, the backward regenerates the mask from `seed`.  A rating outside [0, num_ratings) is clamped (memory
+ * safety; it is the caller's error).  Do <= HSTU_PREPROCESS_MAX_DIM, N' <= num_positions, batch * N' < 2^31.  batch == 0
+ * or n == 0: returns without a launch.  No host synchronisation; nothing is read back. */
+#define HSTU_PREPROCESS_PLAIN 0
+#define HSTU_PREPROCESS_CONCAT 1
+#define HSTU_PREPROCESS_INTERLEAVE 2
+#define HSTU_PREPROCESS_MAX_DIM 4096
+int hstu_input_preprocess_fwd(const int64_t* past_ids, const void* past_embeddings, const void* ratings, const void* pos_table,
+                              const void* rating_table, void* out, float* valid_mask, int32_t batch, int32_t n,
+                              int32_t item_dim, int32_t rating_dim, int32_t num_positions, int32_t num_ratings, int layout,
+                              float dropout_ratio, uint64_t seed, int emb_dtype, int out_dtype, int rating_index_dtype,
+                              void* stream);
+/* Given d_out (batch, N', Do) in `out_dtype` and h = d_out * m * keep * scale (fp32):
+ *   d_past_embeddings = fl(h s) in `emb_dtype`;  d_pos_table[n', :] = sum_b h[b, n', :], rows >= N' zero;
+ *   d_rating_table[r, :] = s * sum of h over the rating columns (CONCAT) / odd rows (INTERLEAVE) of the (b, i) with rating r.
+ * Both table gradients are fp32 (num_positions, Do) / (num_ratings, rating_dim), summed in a fixed order -- per-thread
+ * running sums over slabs of users (rows), the slabs added in order by a second kernel; no float atomics, bit-identical
+ * run to run.  Any of the three outputs may be NULL and is then not computed.  `workspace`:
+ * hstu_input_preprocess_bwd_workspace_bytes(...) bytes of device memory, 32-byte aligned (needed for the table gradients). */
+size_t hstu_input_preprocess_bwd_workspace_bytes(int32_t batch, int32_t n, int32_t item_dim, int32_t rating_dim,
+                                                 int32_t num_ratings, int layout);
+int hstu_input_preprocess_bwd(const void* d_out, const int64_t* past_ids, const void* ratings, void* d_past_embeddings,
+                              float* d_pos_table, float* d_rating_table, void* workspace, int32_t batch, int32_t n,
+                              int32_t item_dim, int32_t rating_dim, int32_t num_positions, int32_t num_ratings, int layout,
+                              float dropout_ratio, uint64_t seed, int emb_dtype, int out_dtype, int rating_index_dtype,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
