@@ -393,6 +393,25 @@ int hstu_embedding_grad(const void* dout, const int32_t* idx, int64_t n, int32_t
 int hstu_embedding_grad_segment_sum(const void* dout, const int64_t* sorted_rows, const int32_t* sorted_idx, int64_t n,
                                     int32_t dim, int32_t table_rows, float* table_grad, int dtype, void* stream);
 
+/* In-backward sparse row-wise Adagrad of one embedding table (the reference's DLRM-v3 training: RowWiseAdagrad applied
+ * in backward, dlrm_v3/train/utils.py:190-227; weight_decay = 0, lr_decay = 0).  For every table row r that occurs in idx,
+ * and only for those rows:
+ *   G[r, :] = sum over e with idx[e] == r of dout[e, :]   (fp32; duplicates in batch order inside a chunk of 128 sorted
+ *             rows -- 32 below 262,144 ids with dim <= 512 --, the pieces of a run that crosses chunks in position order)
+ *   momentum1[r] += mean_d(G[r, d]^2);   weight[r, :] -= lr / (sqrt(momentum1[r]) + eps) * G[r, :]
+ * in place; every other row of weight (table_rows, dim) fp32 and momentum1 (table_rows) fp32 keeps its bits.  No
+ * table-sized temporary, no float atomics, no host synchronisation: results are bit-identical from run to run.  dout
+ * (n, dim) in `dtype` (bf16 / fp16 / fp32), rows 16-byte multiples of at most 4 KiB, dout and weight 16-byte aligned;
+ * n <= 2^31 - 1, n == 0 touches nothing.  0 <= idx[e] < table_rows is the caller's duty (not checked, as for
+ * hstu_embedding_grad).  `workspace`: device memory, 256-byte aligned, at least
+ * hstu_embedding_rowwise_adagrad_workspace_bytes(n, table_rows) bytes: O(n) and independent of table_rows and dim -- 8
+ * bytes per id for the sorted pairs, the sort's temporary, and two partial sums of the widest row (8 KiB) per 128 ids,
+ * i.e. 128 bytes per id. */
+int hstu_embedding_rowwise_adagrad_workspace_bytes(int64_t n, int32_t table_rows, int64_t* bytes);
+int hstu_embedding_rowwise_adagrad(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows,
+                                   float* weight, float* momentum1, float lr, float eps, void* workspace,
+                                   int64_t workspace_bytes, int dtype, void* stream);
+
 /* ---- output postprocessor: row L2 normalisation ---------------------------------------------------------
  * y = x / max(||x||_2, eps) per row of (rows, dim), and its backward.  Replaces L2NormPostprocessor.forward
  * (modules/postprocessors.py:55-69: seq / linalg.norm(seq, dim=-1).clamp(min=1e-6)) and its autograd. */

@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""In-backward sparse row-wise Adagrad on one MI355X: the fused step (ops/embedding.py: sort, one pass over the batch's gradient
+rows and the touched table rows, one pass that combines the runs cut by a chunk boundary) against what the package did for the
+same ids before it existed -- the dense table gradient of ``_table_grad`` (memset + segment sum over the whole table) followed
+by the same formula over the dense table in torch ops.  One JSON object on stdout, and in --out.
+
+bf16 gradient rows, dim 256, Zipf ids scattered over the table:
+    1 M rows,  n = 65,536 and n = 1,638,400: both paths (the dense gradient and the dense update fit at this size);
+    10 M rows (the reference's HASH_SIZE), the same two n: the fused path alone (the dense path's temporaries would be 10 GB each).
+Both paths run in ONE process on the same inputs, timed with HIP events after a warm-up, alternating fused / dense rounds; the
+median per call is reported.  The state keeps changing from call to call (the step is in place), which changes no address and
+no amount of work.  Bytes are algorithmic: n * dim * sizeof(dout) + unique * (2 * dim * 4 + 8) -- every gradient row read
+once, every touched table row and its state read and written once; GB/s is those bytes over the time, share_of_8TBs the
+same over 8 TB/s.
+
+    python tools/bench_embedding_optimizer.py [--iters 10] [--rounds 7] [--out profiles/r15_bench_embedding_optimizer.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from generative_recommenders_amd.ops.embedding import rowwise_adagrad_update_  # noqa: E402
+from generative_recommenders_amd.ops.position import _table_grad  # noqa: E402
+
+DEV = "cuda"
+DIM, LR, EPS = 256, 0.01, 1e-8
+# name: (table rows, n, time the dense path too)
+SHAPES = {"1Mx256_n65536": (1_000_000, 65_536, True), "1Mx256_n1638400": (1_000_000, 1_638_400, True),
+          "10Mx256_n65536": (10_000_000, 65_536, False), "10Mx256_n1638400": (10_000_000, 1_638_400, False)}
+
+
+def _events_ms(fn, iters):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(iters):
+        fn()
+    e.record()
+    e.synchronize()
+    return s.elapsed_time(e) / iters
+
+
+def _zipf_ids(rows, n, g):
+    """rank r with probability ~ 1 / (r + 1); the ranks scattered over the table"""
+    p = 1.0 / torch.arange(1, rows + 1, dtype=torch.float32, device=DEV)
+    cdf = torch.cumsum(p.double(), 0)
+    ranks = torch.searchsorted(cdf, torch.rand(n, device=DEV, generator=g, dtype=torch.float64) * cdf[-1]).clamp_(max=rows - 1)
+    return ((ranks * 2_654_435_761) % rows).to(torch.int64)       # a fixed odd multiplier: hot ranks land far apart
+
+
+def _dense_step(weight, momentum1, idx32, dout):
+    """the parent's path for the same ids: the dense (rows, dim) fp32 gradient, then the formula over the whole table (rows
+    outside the batch have a zero gradient row: their state and weights keep their values)"""
+    grad = _table_grad(dout, idx32, weight.shape[0])
+    momentum1.add_(grad.pow(2).mean(dim=1))
+    weight.addcdiv_(grad, (momentum1.sqrt() + EPS).unsqueeze(1), value=-LR)
+
+
+def run(rows, n, dense, iters, rounds):
+    g = torch.Generator(device=DEV).manual_seed(0)
+    idx = _zipf_ids(rows, n, g)
+    idx32 = idx.to(torch.int32)
+    counts = torch.bincount(idx, minlength=1)
+    unique = int((counts > 0).sum())
+    dout = (0.01 * torch.randn(n, DIM, device=DEV, generator=g)).to(torch.bfloat16)
+    weight = torch.randn(rows, DIM, device=DEV, generator=g)
+    momentum1 = torch.zeros(rows, device=DEV)
+    paths = {"fused": lambda: rowwise_adagrad_update_(weight, momentum1, idx32, dout, LR, EPS)}
+    res = {"shape": {"table_rows": rows, "dim": DIM, "n": n, "unique_ids": unique, "largest_multiplicity": int(counts.max()),
+                     "dout": "bfloat16"}}
+    del counts
+    if dense:
+        w2, m2 = weight.clone(), momentum1.clone()
+        paths["dense"] = lambda: _dense_step(w2, m2, idx32, dout)
+        for fn in paths.values():                                  # one step each from the same state: the results to compare
+            fn()
+        res["max_abs_diff_after_one_step"] = {"weight": float((weight - w2).abs().max()), "momentum1": float((momentum1 - m2).abs().max())}
+    for fn in paths.values():                                      # warm-up of every shape of the timed window
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in paths}
+    for _ in range(rounds):
+        for name, fn in paths.items():
+            times[name].append(_events_ms(fn, iters))
+    alg_bytes = n * DIM * dout.element_size() + unique * (2 * DIM * 4 + 8)
+    res["algorithmic_bytes"] = alg_bytes
+    res["us"] = {k: round(1e3 * statistics.median(v), 2) for k, v in times.items()}
+    res["us_rounds"] = {k: [round(1e3 * x, 2) for x in v] for k, v in times.items()}
+    res["GBps"] = {k: round(alg_bytes / (1e-3 * statistics.median(v)) / 1e9, 1) for k, v in times.items()}
+    res["share_of_8TBs"] = {k: round(alg_bytes / (1e-3 * statistics.median(v)) / 8e12, 4) for k, v in times.items()}
+    if dense:
+        res["dense_over_fused"] = round(statistics.median(times["dense"]) / statistics.median(times["fused"]), 2)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--shapes", default=",".join(SHAPES))
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_embedding_optimizer: needs a GPU (a timing without one says nothing)")
+    res = {"device": torch.cuda.get_device_name(0), "iters": args.iters, "rounds": args.rounds, "workloads": {}}
+    for name in args.shapes.split(","):
+        res["workloads"][name] = run(*SHAPES[name], args.iters, args.rounds)
+        torch.cuda.empty_cache()
+    text = json.dumps(res)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(text + "\n")
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
