@@ -144,6 +144,7 @@ SIGNATURES = {
                                         _i32, _f32, _vp, _vp, _int, _vp]),
     "hstu_sampled_softmax_bwd": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _f32, _i32,
                                         _i32, _f32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _int, _vp]),
+    "hstu_mol_scores": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _int, _int, _vp]),
     "hstu_multitask_head_workspace_bytes": (C.c_size_t, [_i32, _i32]),
     "hstu_multitask_head_fwd": (_int, [_vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32,
                                        _i32, _i32, _f32, _int, _vp]),

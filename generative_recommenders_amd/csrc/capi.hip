@@ -276,6 +276,33 @@ int hstu_mips_topk(const void* queries, int64_t q_row_stride, const void* items,
                           dtype, (hipStream_t)stream);
 }
 
+int hstu_mol_scores(const void* qc, const void* xc, const void* gq, const void* gi, const void* w1, const void* b1, const void* w2,
+                    const void* b2, float* out, int32_t batch, int32_t num_items, int32_t pq, int32_t px, int32_t dim,
+                    int32_t hidden, float inv_temperature, int combination, int dtype, void* stream) {
+  const char* who = "hstu_mol_scores";
+  if (dtype != HSTU_DTYPE_BF16 && dtype != HSTU_DTYPE_F16 && dtype != HSTU_DTYPE_F32)
+    return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32 (got code %d)", who, dtype);
+  if (combination != HSTU_MOL_GLU_SILU && combination != HSTU_MOL_GLU_SILU_LN)
+    return set_error(HSTU_EINVAL, "%s: combination must be HSTU_MOL_GLU_SILU or HSTU_MOL_GLU_SILU_LN (got %d)", who, combination);
+  if (batch < 0 || num_items < 0) return set_error(HSTU_EINVAL, "%s: negative batch or num_items", who);
+  if (pq < 1 || px < 1 || (int64_t)pq * px > kMolMaxLogits)
+    return set_error(HSTU_EUNSUPPORTED, "%s: %d x %d logits; 1 <= P_Q, P_X and P_Q * P_X <= %d are built", who, pq, px, kMolMaxLogits);
+  if (dim < 1 || dim > kMolMaxDim || dim % 8)
+    return set_error(HSTU_EUNSUPPORTED, "%s: dot product dimension %d; multiples of 8 up to %d are built (zero-pad it)", who, dim,
+                     kMolMaxDim);
+  if (hidden < 0 || hidden > kMolMaxHidden)
+    return set_error(HSTU_EUNSUPPORTED, "%s: %d hidden units; 0 <= H <= %d are built", who, hidden, kMolMaxHidden);
+  if (batch == 0 || num_items == 0) return HSTU_OK;
+  if (!qc || !xc || !gq || !gi || !w1 || !b2 || !out || (hidden > 0 && (!b1 || !w2)))
+    return set_error(HSTU_EINVAL, "%s: operands, weights and out must be non-NULL", who);
+  const int eb = dtype == HSTU_DTYPE_F32 ? 4 : 2;
+  if ((((uintptr_t)qc | (uintptr_t)xc) & 15) || (((uintptr_t)gq | (uintptr_t)gi | (uintptr_t)w1 | (uintptr_t)b1 | (uintptr_t)w2 | (uintptr_t)b2) & (eb - 1)) ||
+      ((uintptr_t)out & 3))
+    return set_error(HSTU_EINVAL, "%s: qc and xc must be 16-byte aligned, the other operands element aligned", who);
+  return launch_mol_scores(qc, xc, gq, gi, w1, b1, w2, b2, out, batch, num_items, pq, px, dim, hidden, inv_temperature,
+                           combination == HSTU_MOL_GLU_SILU_LN, dtype, (hipStream_t)stream);
+}
+
 // ---- multitask prediction head --------------------------------------------------------------------------------------------
 static int validate_multitask(const char* who, const void* x, int64_t x_rs, const void* dx, int64_t dx_rs, const void* ln_w,
                               const void* ln_b, int64_t rows, int32_t dim, int32_t tasks, int32_t nbin, int dtype,

@@ -114,6 +114,15 @@ size_t mips_topk_workspace_bytes(int batch, int k);
 int launch_mips_topk(const void* queries, int64_t q_rs, const void* items, int64_t i_rs, void* out_scores, int32_t* out_indices,
                      void* workspace, int batch, int num_items, int dim, int k, int dtype, hipStream_t st);
 
+// Mixture-of-Logits scores (mol_ops.hip): logits, gating MLP, gate and softmax-weighted sum per (query, item) pair in
+// registers and LDS; arguments as validated by capi.hip
+constexpr int kMolMaxLogits = HSTU_MOL_MAX_LOGITS;
+constexpr int kMolMaxDim = HSTU_MOL_MAX_DIM;
+constexpr int kMolMaxHidden = HSTU_MOL_MAX_HIDDEN;
+int launch_mol_scores(const void* qc, const void* xc, const void* gq, const void* gi, const void* w1, const void* b1, const void* w2,
+                      const void* b2, float* out, int batch, int num_items, int pq, int px, int dim, int hidden, float inv_temperature,
+                      int layer_norm, int dtype, hipStream_t st);
+
 // multitask prediction head (multitask_ops.hip): SwishLayerNorm + task projection + predictions + task losses per row, and
 // the backward; arguments as validated by capi.hip.  `vec`: rows are read as 16-byte pieces (dim, pointers and row strides
 // allow it), else element by element -- the two dim limits are those of hstu_swish_layer_norm_fwd

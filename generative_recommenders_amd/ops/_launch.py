@@ -536,6 +536,44 @@ def mips_topk(queries: torch.Tensor, items: torch.Tensor, k: int) -> Tuple[torch
     return scores, indices
 
 
+# ----------------------------------------------------------------------------- Mixture-of-Logits
+MOL_MAX_LOGITS, MOL_MAX_DIM, MOL_MAX_HIDDEN = 64, 128, 256       # HSTU_MOL_MAX_* of include/hstu_hip.h
+MOL_COMBINATIONS = {"glu_silu": 0, "glu_silu_ln": 1}
+
+
+def mol_scores(qc: torch.Tensor, xc: torch.Tensor, gq: torch.Tensor, gi: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tensor],
+               w2: Optional[torch.Tensor], b2: torch.Tensor, inv_temperature: float, combination: str) -> torch.Tensor:
+    """Mixture-of-Logits scores of every (query, item) pair (hstu_mol_scores): qc (B, P_Q, D), xc (X, P_X, D), gq (B, L),
+    gi (X, L), the gating MLP w1 (H, L), b1 (H), w2 (L, H), b2 (L) -- or one layer w1 (L, L), b2 (L) with b1 = w2 = None -- all
+    of one bf16 / fp16 / fp32 dtype -> (B, X) fp32.  Contiguous operands are used as they are; the library judges the shape."""
+    names = ("qc", "xc", "gq", "gi", "w1", "b1", "w2", "b2")
+    tensors = (qc, xc, gq, gi, w1, b1, w2, b2)
+    for name, t in zip(names, tensors):
+        if t is None:
+            continue
+        L.require_gpu_tensor(t, name)
+        if t.dtype != qc.dtype or t.device != qc.device:
+            raise RuntimeError(f"mol_scores: {name} is {t.dtype} on {t.device}, qc is {qc.dtype} on {qc.device}")
+    if combination not in MOL_COMBINATIONS:
+        raise RuntimeError(f"mol_scores: combination {combination!r} has no kernel (built: {sorted(MOL_COMBINATIONS)})")
+    if qc.dim() != 3 or xc.dim() != 3 or qc.shape[2] != xc.shape[2]:
+        raise RuntimeError(f"mol_scores: qc (B, P_Q, D) and xc (X, P_X, D) expected, got {tuple(qc.shape)} and {tuple(xc.shape)}")
+    B, PQ, D = qc.shape
+    X, PX, _ = xc.shape
+    nl = PQ * PX
+    H = w1.shape[0] if w2 is not None else 0
+    if ((b1 is None) != (w2 is None) or gq.shape != (B, nl) or gi.shape != (X, nl) or b2.shape != (nl,)
+            or w1.shape != ((H, nl) if H else (nl, nl)) or (H and (w2.shape != (nl, H) or b1.shape != (H,)))):
+        raise RuntimeError(f"mol_scores: operand shapes do not fit P_Q = {PQ}, P_X = {PX}, H = {H}")
+    out = torch.empty((B, X), dtype=torch.float32, device=qc.device)
+    ptr = [t.contiguous() if t is not None else None for t in tensors]
+    args = [t.data_ptr() if t is not None else None for t in ptr]
+    with torch.cuda.device(qc.device):
+        L.check(L.lib().hstu_mol_scores(*args, out.data_ptr(), B, X, PQ, PX, D, H, float(inv_temperature), MOL_COMBINATIONS[combination],
+                                        L.torch_dtype_code(qc.dtype), L.current_stream_ptr(qc.device)))
+    return out
+
+
 # ----------------------------------------------------------------------------- norms
 def _f32(n, device):
     return torch.empty(n, dtype=torch.float32, device=device)

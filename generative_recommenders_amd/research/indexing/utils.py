@@ -4,12 +4,19 @@ import torch
 
 from generative_recommenders_amd.research.rails.indexing.candidate_index import TopKModule
 from generative_recommenders_amd.research.rails.indexing.mips_top_k import MIPSBruteForceTopK
+from generative_recommenders_amd.research.rails.indexing.mol_top_k import MoLBruteForceTopK
+from generative_recommenders_amd.research.rails.similarities.mol.similarity_fn import MoLSimilarity
 
 
 def get_top_k_module(top_k_method: str, model: torch.nn.Module, item_embeddings: torch.Tensor, item_ids: torch.Tensor) -> TopKModule:
     if top_k_method == "MIPSBruteForceTopK":
         return MIPSBruteForceTopK(item_embeddings=item_embeddings, item_ids=item_ids)
     if top_k_method == "MoLBruteForceTopK":
-        raise ValueError("top-k method MoLBruteForceTopK is not built in this package (mixture-of-logits retrieval has no "
-                         "HIP kernel here); use MIPSBruteForceTopK")
+        # the similarity is the model's ``_ndp_module`` (the reference's helper, research/indexing/utils.py:37-41, passes
+        # no ``mol_module`` at all and cannot work)
+        mol_module = getattr(model, "_ndp_module", None)
+        if not isinstance(mol_module, MoLSimilarity):
+            raise ValueError(f"top-k method MoLBruteForceTopK is not built for {type(model).__name__}: its _ndp_module is "
+                             f"{type(mol_module).__name__}, not a MoLSimilarity; use MIPSBruteForceTopK")
+        return MoLBruteForceTopK(mol_module=mol_module, item_embeddings=item_embeddings, item_ids=item_ids)
     raise ValueError(f"Invalid top-k method {top_k_method}")

@@ -517,6 +517,33 @@ int hstu_mips_topk(const void* queries, int64_t q_row_stride, const void* items,
                    int32_t* out_indices, void* workspace, int32_t batch, int32_t num_items, int32_t dim, int32_t k, int dtype,
                    void* stream);
 
+/* ---- Mixture-of-Logits scores: every (query, item) pair against a shared table, no (batch, num_items, L) tensor ----
+ * With L = pq * px, for every query b and item x (fp32 accumulation and intermediates):
+ *   l[n px + m] = <qc[b, n, :], xc[x, m, :]> * inv_temperature            (the reference's "bxnm" reshape order)
+ *   t           = w2 silu(w1 l + b1) + b2        hidden > 0: w1 (hidden, L), b1 (hidden), w2 (L, hidden), b2 (L)
+ *               = w1 l + b2                      hidden == 0: w1 (L, L), b2 (L); b1 and w2 are not read
+ *   g           = gq[b] * gi[x] + t
+ *   w           = g sigmoid(g)                   combination HSTU_MOL_GLU_SILU
+ *               = g sigmoid(layer_norm(g))       combination HSTU_MOL_GLU_SILU_LN (no affine, eps 1e-5)
+ *   out[b, x]   = sum_j softmax(w)_j l_j
+ * Replaces MoLSimilarity.forward + MoLGatingFn.forward + SoftmaxDropoutCombiner in eval mode for a shared item table
+ * (research/rails/similarities/mol/similarity_fn.py:363-387, :151-204, :35-49), which materialise the (B, X, L) logits
+ * and the (B, X, hidden) layer.  qc (batch, pq, dim), xc (num_items, px, dim), gq (batch, L), gi (num_items, L) and the
+ * weights: contiguous, all in `dtype` (bf16, fp16, fp32); qc and xc 16-byte aligned.  out (batch, num_items) contiguous
+ * fp32, addressed in 64 bits.  fp32 operands use the exact fp32 MFMA; 16-bit operands are rounded to `dtype` where an MFMA
+ * reads them.  No atomics: bit-identical run to run.  HSTU_EUNSUPPORTED before any launch unless 1 <= pq, px and
+ * L <= HSTU_MOL_MAX_LOGITS, 1 <= dim <= HSTU_MOL_MAX_DIM with dim a multiple of 8 (zero-pad it: a dot product does not
+ * change), 0 <= hidden <= HSTU_MOL_MAX_HIDDEN.  batch, num_items < 2^31 (a batch above 4 * 2^20 queries runs as several
+ * launches on `stream`); either == 0 returns without a launch. */
+#define HSTU_MOL_MAX_LOGITS 64
+#define HSTU_MOL_MAX_DIM 128
+#define HSTU_MOL_MAX_HIDDEN 256
+#define HSTU_MOL_GLU_SILU 0
+#define HSTU_MOL_GLU_SILU_LN 1
+int hstu_mol_scores(const void* qc, const void* xc, const void* gq, const void* gi, const void* w1, const void* b1, const void* w2,
+                    const void* b2, float* out, int32_t batch, int32_t num_items, int32_t pq, int32_t px, int32_t dim,
+                    int32_t hidden, float inv_temperature, int combination, int dtype, void* stream);
+
 /* ---- multitask prediction head: SwishLayerNorm + task projection + predictions + task losses in one row pass ----
  * Per row l of x (rows, dim; `dtype`, row stride in elements, unit column stride), fp32 math throughout:
  *   y = x * sigmoid(LayerNorm(x) ln_weight + ln_bias)                  (never written to memory)
