@@ -11,47 +11,15 @@
 
 namespace hstu {
 
-template <typename T, int D>
-static int launch_bwd_fold_inst(const HstuAttnBwdParams& bp, hipStream_t st) {
-  using F = FoldCfg<T, D, D>;
-  const HstuAttnParams& p = bp.fwd;
-  const int tmax = (p.max_seq_len + 31) / 32;
-  const int smem = F::smem_bytes();
-  auto kern = hstu_attn_bwd_fold_kernel<T, D, D>;
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) return set_error(HSTU_ELAUNCH, "hstu_attn_bwd: cannot reserve %d bytes of LDS: %s", smem, hipGetErrorString(e));
-  }
-  // one persistent workgroup per CU (never more workgroups than problems: every workgroup reads its first problem's offsets)
-  int grid = p.batch * p.heads;
-  const int n_cu = cu_count();
-  if (grid > n_cu) grid = n_cu;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kBwdThreads), smem, st, bp, tmax);
-  return check_launch("hstu_attn_bwd(fold)");
-}
-
-// head dim 64: 4-wave workgroups, two per CU (hstu_attn_bwd_quad.cuh)
-template <typename T, int D>
-static int launch_bwd_quad_inst(const HstuAttnBwdParams& bp, hipStream_t st) {
-  using Q = QuadCfg<T, D>;
-  const HstuAttnParams& p = bp.fwd;
-  const int tmax = (p.max_seq_len + 31) / 32;
-  const int smem = Q::smem_bytes();
-  static_assert(Q::smem_bytes() <= 80 * 1024, "two workgroups per CU");
-  auto kern = hstu_attn_bwd_quad_kernel<T, D>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  if (e != hipSuccess) return set_error(HSTU_ELAUNCH, "hstu_attn_bwd: cannot reserve %d bytes of LDS: %s", smem, hipGetErrorString(e));
-  const int grid = p.batch * p.heads;   // one workgroup per problem
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kQuadThreads), smem, st, bp, tmax);
-  return check_launch("hstu_attn_bwd(quad)");
-}
-
+// folded schedule: one persistent workgroup per CU; head dim 64 (kSchedQuad): 4-wave workgroups, two per CU, one per problem
 template <typename T>
-static int launch_bwd_fold_dtype(const HstuAttnBwdParams& bp, hipStream_t st) {
-  if (bp.fwd.dqk == 128) return launch_bwd_fold_inst<T, 128>(bp, st);
-  if (bp.fwd.dqk == 64 && attn_bwd_quad_applicable(bp)) return launch_bwd_quad_inst<T, 64>(bp, st);
-  if (bp.fwd.dqk == 64) return launch_bwd_fold_inst<T, 64>(bp, st);
-  return set_error(HSTU_EUNSUPPORTED, "hstu_attn_bwd(fold): head dim %d not instantiated", bp.fwd.dqk);
+int launch_bwd_fold(const AttnPlan& pl, const HstuAttnBwdParams& bp, hipStream_t st) {
+  const AttnLaunch& l = pl.launch[0];
+  const bool quad = pl.sched == kSchedQuad;
+  auto kern = quad ? hstu_attn_bwd_quad_kernel<T, 64> : (pl.a == 128 ? hstu_attn_bwd_fold_kernel<T, 128, 128> : hstu_attn_bwd_fold_kernel<T, 64, 64>);
+  if (int e = reserve_lds((const void*)kern, l.smem, "hstu_attn_bwd")) return e;
+  hipLaunchKernelGGL(kern, dim3(l.grid), dim3(quad ? kQuadThreads : kBwdThreads), l.smem, st, bp, pl.nw);
+  return check_launch(quad ? "hstu_attn_bwd(quad)" : "hstu_attn_bwd(fold)");
 }
 
 }  // namespace hstu

@@ -1,5 +1,5 @@
 // f16 instantiations of the folded backward schedule.
 #include "attn_fold.cuh"
 namespace hstu {
-int launch_attn_bwd_fold_f16(const HstuAttnBwdParams& p, hipStream_t st) { return launch_bwd_fold_dtype<f16_t>(p, st); }
+template int launch_bwd_fold<f16_t>(const AttnPlan&, const HstuAttnBwdParams&, hipStream_t);
 }  // namespace hstu

@@ -2,5 +2,5 @@
 #include "capi_internal.h"
 #include "hstu_attn_bwd_long.cuh"
 namespace hstu {
-int launch_attn_bwd_long_bf16(const HstuAttnBwdParams& p, hipStream_t st) { return launch_bwd_long_dtype<bf16_t>(p, st); }
+template int launch_bwd_long<bf16_t>(const AttnPlan&, const HstuAttnBwdParams&, hipStream_t);
 }  // namespace hstu

@@ -98,11 +98,13 @@ int hstu_attn_fwd(const HstuAttnParams* p, void* stream) {
   if (((p->o_row_stride | p->o_head_stride) * (p->dtype == HSTU_DTYPE_F32 ? 4 : 2)) % 16 || ((uintptr_t)p->out & 15))
     return set_error(HSTU_EINVAL, "hstu_attn_fwd: out rows must be 16-byte aligned");
   if (p->batch == 0) return HSTU_OK;   // empty batch: nothing to launch (flash_common.cpp:548-551)
+  const AttnPlan pl = plan_attn_fwd(*p);
+  if (pl.err) return set_error(pl.err, "%s", pl.msg);
   hipStream_t st = (hipStream_t)stream;
   switch (p->dtype) {
-    case HSTU_DTYPE_BF16: return launch_attn_fwd_bf16(*p, st);
-    case HSTU_DTYPE_F16: return launch_attn_fwd_f16(*p, st);
-    default: return launch_attn_fwd_f32(*p, st);
+    case HSTU_DTYPE_BF16: return launch_attn_fwd<bf16_t>(pl, *p, st);
+    case HSTU_DTYPE_F16: return launch_attn_fwd<f16_t>(pl, *p, st);
+    default: return launch_attn_fwd<float>(pl, *p, st);
   }
 }
 
@@ -123,7 +125,7 @@ int hstu_attn_fwd_kernel_name(const HstuAttnParams* p, char* buf, size_t len) {
     snprintf(buf, len, "hstu_attn_fwd_fp8_kernel<fp8,%d,%d>", fp8_head_dim(p->dqk), fp8_head_dim(p->dv));
     return HSTU_OK;
   }
-  return attn_kernel_name(*p, nullptr, buf, len);
+  return attn_kernel_name(plan_attn_fwd(*p), buf, len);
 }
 
 int hstu_attn_bwd_kernel_name(const HstuAttnBwdParams* p, char* buf, size_t len) {
@@ -132,12 +134,12 @@ int hstu_attn_bwd_kernel_name(const HstuAttnBwdParams* p, char* buf, size_t len)
     if (buf && len) buf[0] = 0;
     return set_error(HSTU_EUNSUPPORTED, "hstu_attn_bwd: fp8 (e4m3) attention is forward-only");
   }
-  return attn_kernel_name(p->fwd, p, buf, len);
+  return attn_kernel_name(plan_attn_bwd(*p), buf, len);
 }
 
 size_t hstu_attn_bwd_workspace_bytes(const HstuAttnBwdParams* p) {
   if (!p || p->fwd.dtype == HSTU_DTYPE_FP8_E4M3) return 0;
-  return attn_bwd_workspace_bytes(*p);
+  return plan_attn_bwd(*p).ws_bytes;
 }
 
 int hstu_attn_bwd(const HstuAttnBwdParams* p, void* stream) {
@@ -161,13 +163,14 @@ int hstu_attn_bwd(const HstuAttnBwdParams* p, void* stream) {
     return set_error(HSTU_EUNSUPPORTED, "hstu_attn_bwd: deterministic = 1 is not available with the relative bias (the table gradients are "
                                         "histograms of float atomics)");
   if (p->fwd.batch == 0 || p->total_rows == 0) return HSTU_OK;
-  if (attn_bwd_workspace_bytes(*p) > 0 && !p->workspace)
-    return set_error(HSTU_EINVAL, "hstu_attn_bwd: this shape needs %zu bytes of workspace", attn_bwd_workspace_bytes(*p));
+  const AttnPlan pl = plan_attn_bwd(*p);
+  if (pl.ws_bytes > 0 && !p->workspace) return set_error(HSTU_EINVAL, "hstu_attn_bwd: this shape needs %zu bytes of workspace", pl.ws_bytes);
+  if (pl.err) return set_error(pl.err, "%s", pl.msg);
   hipStream_t st = (hipStream_t)stream;
   switch (p->fwd.dtype) {
-    case HSTU_DTYPE_BF16: return launch_attn_bwd_bf16(*p, st);
-    case HSTU_DTYPE_F16: return launch_attn_bwd_f16(*p, st);
-    default: return launch_attn_bwd_f32(*p, st);
+    case HSTU_DTYPE_BF16: return launch_attn_bwd<bf16_t>(pl, *p, st);
+    case HSTU_DTYPE_F16: return launch_attn_bwd<f16_t>(pl, *p, st);
+    default: return launch_attn_bwd<float>(pl, *p, st);
   }
 }
 

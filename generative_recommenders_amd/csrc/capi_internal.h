@@ -8,64 +8,75 @@ namespace hstu {
 int set_error(int code, const char* fmt, ...);   // records the message, returns `code`
 int check_launch(const char* what);              // hipGetLastError() -> HSTU_OK | HSTU_ELAUNCH
 
-// per-dtype attention launchers (one translation unit each, so they compile in parallel)
-int launch_attn_fwd_bf16(const HstuAttnParams& p, hipStream_t st);
-int launch_attn_fwd_f16(const HstuAttnParams& p, hipStream_t st);
-int launch_attn_fwd_f32(const HstuAttnParams& p, hipStream_t st);
-int launch_attn_bwd_bf16(const HstuAttnBwdParams& p, hipStream_t st);
-int launch_attn_bwd_f16(const HstuAttnBwdParams& p, hipStream_t st);
-int launch_attn_bwd_f32(const HstuAttnBwdParams& p, hipStream_t st);
-int launch_attn_fwd_bias_bf16(const HstuAttnParams& p, hipStream_t st);
-int launch_attn_fwd_bias_f16(const HstuAttnParams& p, hipStream_t st);
-int launch_attn_fwd_bias_f32(const HstuAttnParams& p, hipStream_t st);
-int launch_attn_bwd_bias_bf16(const HstuAttnBwdParams& p, hipStream_t st);
-int launch_attn_bwd_bias_f16(const HstuAttnBwdParams& p, hipStream_t st);
-int launch_attn_bwd_bias_f32(const HstuAttnBwdParams& p, hipStream_t st);
-// folded schedule of the backward for short sequences (hstu_attn_bwd_fold.cuh); 16-bit dtypes only
-int launch_attn_bwd_fold_bf16(const HstuAttnBwdParams& p, hipStream_t st);
-int launch_attn_bwd_fold_f16(const HstuAttnBwdParams& p, hipStream_t st);
-bool attn_bwd_fold_applicable(const HstuAttnBwdParams& p);
-// long sequences (more than one key block), 16-bit I/O, no bias, no contextual rows: dK / dV kernel + dQ kernel, no atomics, no
-// workspace (hstu_attn_bwd_long.cuh; HSTU_BWD_LONG=0: the general kernel, A/B measurements)
-int launch_attn_bwd_long_bf16(const HstuAttnBwdParams& p, hipStream_t st);
-int launch_attn_bwd_long_f16(const HstuAttnBwdParams& p, hipStream_t st);
-bool attn_bwd_long_applicable(const HstuAttnBwdParams& p);
-// short sequences (max_seq_len <= 64, head dims <= 32, 16-bit I/O): one wave per (user, head) (hstu_attn_solo.cuh; HSTU_SOLO=0 disables)
-int launch_attn_fwd_solo_bf16(const HstuAttnParams& p, hipStream_t st);
-int launch_attn_fwd_solo_f16(const HstuAttnParams& p, hipStream_t st);
-int launch_attn_bwd_solo_bf16(const HstuAttnBwdParams& p, hipStream_t st);
-int launch_attn_bwd_solo_f16(const HstuAttnBwdParams& p, hipStream_t st);
-bool attn_solo_applicable(const HstuAttnParams& p, bool backward);
-// the same shapes with the research path's relative bias (hstu_attn_{fwd,bwd}_solo_bias_kernel; HSTU_SOLO_BIAS=0 disables)
-int launch_attn_fwd_solo_bias_bf16(const HstuAttnParams& p, hipStream_t st);
-int launch_attn_fwd_solo_bias_f16(const HstuAttnParams& p, hipStream_t st);
-int launch_attn_bwd_solo_bias_bf16(const HstuAttnBwdParams& p, hipStream_t st);
-int launch_attn_bwd_solo_bias_f16(const HstuAttnBwdParams& p, hipStream_t st);
-bool attn_solo_bias_applicable(const HstuAttnParams& p, bool backward);
-bool attn_solo_bias_lds(const HstuAttnParams& p, int base, int cache, int* ts_copies, int* hist_bytes, int* smem);
-// ... and, among those, the ones the 4-wave / two-workgroups-per-CU kernel takes (head dim 64; HSTU_BWD_QUAD=0 disables)
-bool attn_bwd_quad_applicable(const HstuAttnBwdParams& p);
-// sums the per-workgroup bias-gradient rows: partial (rows, width) -> dpos_w (npos), dts_w (width - npos)
-int launch_bias_grad_reduce(const float* partial, int rows, int width, int npos, float* dpos_w, float* dts_w,
-                            hipStream_t st);
-size_t attn_bwd_workspace_bytes(const HstuAttnBwdParams& p);
-// profiler names of the instantiations the launchers above pick (attn_misc.hip)
-int attn_kernel_name(const HstuAttnParams& p, const HstuAttnBwdParams* bwd, char* buf, size_t len);
-int attn_bwd_tiles_per_block(int dtype, int dqk, int dv, int max_seq_len, int extra_lds);
-// LDS bytes of the research-path bias state of a backward workgroup (histograms with *ts_copies privatised copies of
-// the time-bucket histogram + the staged tables) and the number of copies chosen; 0 without bias
-bool attn_bias_head_loop_enabled();
-// HSTU_ATTN_PRECISE=1: the forward's P' as two 16-bit fragments (value + rounding remainder) for 16-bit I/O at 64 x 64 / 128 x 128
-// without bias: output error at the rounding floor of the I/O dtype, ~20-25 % slower (hstu_attn_fwd.cuh, PRECISE)
-bool attn_fwd_precise_enabled();
-// research-path forward, short sequences: does one workgroup per (user, query block) walk the heads (hstu_attn_fwd.cuh,
-// HEADS instantiation)?  ONE decision for the launcher and for attn_kernel_name.  `ring_bytes` = the K/V ring of the
-// instantiation (FwdCfg::SMEM); *tables / *cache = LDS bytes of the staged tables and of the bucket bytes.
-bool attn_fwd_head_loop_applicable(const HstuAttnParams& p, int ring_bytes, int* tables, int* cache);
-int attn_fwd_ring_bytes(int elem_bytes, int dqk_padded, int dv_padded);   // == FwdCfg<T, DQK, DV>::SMEM (checked by the launcher)
-bool attn_bwd_fold_bias_lds(const HstuAttnParams& p, int base, int* ts_copies, int* hist_bytes, int* smem);
-bool attn_bwd_fold_bias_applicable(const HstuAttnBwdParams& bp);
-int attn_bwd_bias_lds(const HstuAttnParams& p, int* ts_copies);
+// ---- attention dispatch (attn_misc.hip) ----
+// One host-side plan decides everything about an attention call exactly once: which kernel family runs, with which grid
+// and LDS bytes, and where every piece of the backward's workspace lies.  The kernel-name functions, the workspace-size
+// function and the launchers read it and decide nothing themselves.
+enum AttnSched : int {
+  kSchedNone = 0,     // refused before a kernel was chosen (plan.err / plan.msg)
+  kSchedSolo,         // short sequences, one wave per (user, head)                  hstu_attn_{fwd,bwd}_solo_kernel
+  kSchedSoloBias,     // ... with the research path's relative bias                  hstu_attn_{fwd,bwd}_solo_bias_kernel
+  kSchedQuad,         // backward, head dim 64, <= 7 tiles: four-wave workgroups     hstu_attn_bwd_quad_kernel
+  kSchedFold,         // backward, <= 7 tiles: folded schedule                       hstu_attn_bwd_fold_kernel
+  kSchedLong,         // backward, longer: dK / dV kernel + dQ kernel                hstu_attn_bwd_{dkv,dq}_kernel
+  kSchedFoldBias,     // backward, relative bias on the folded schedule              hstu_attn_bwd_fold_bias_kernel
+  kSchedGeneral,      // hstu_attn_{fwd,bwd}_kernel (plan.bias / head_loop / precise pick the instantiation)
+};
+struct AttnLaunch {
+  int tpt;                        // solo kernels: tiles per tensor of the instantiation (2, or 1 for the <= 32-row class)
+  int grid, smem;                 // workgroups, dynamic LDS bytes
+  int ts_copies, hist, tables;    // relative bias: the kernel's arguments of these names
+  int len_lo, len_hi;             // solo kernels: the length class (len_lo, len_hi] this launch takes
+  int row0;                       // its first bias-gradient partial row
+};
+struct AttnPlan {
+  int err;                        // HSTU_OK, or the refusal (msg); with a schedule chosen the name is still valid
+  char msg[200];
+  AttnSched sched;
+  int dtype;
+  bool backward;
+  int a, v;                       // padded head dims
+  bool bias, head_loop, precise, contextual;
+  int nw, nkb, nqb;               // key tiles per block, key blocks, query blocks (where the schedule has them)
+  int n_launch;
+  AttnLaunch launch[2];           // solo: the length classes; long: dK / dV, dQ; general: the kernel, the dq conversion
+  // backward workspace: [fp32 dq accumulator: n_slabs x slab_bytes] [partial rows x width floats] [chunk sums: chunks x width]
+  size_t slab_bytes;              // 0: no accumulator (one key block)
+  int n_slabs;
+  size_t partial_off;
+  int partial_rows, partial_width;
+  size_t zero_bytes;              // zeroed from partial_off on: the partial rows and, fold-bias, the user counter behind them
+  size_t counter_off;             // fold-bias: the int the workgroups draw users from (the reduce's chunk sums take its place afterwards)
+  int red_chunks;
+  size_t chunk_off;
+  size_t ws_bytes;                // the end of everything above
+};
+AttnPlan plan_attn_fwd(const HstuAttnParams& p);
+AttnPlan plan_attn_bwd(const HstuAttnBwdParams& bp);
+int attn_kernel_name(const AttnPlan& pl, char* buf, size_t len);   // profiler name of the instantiation the plan launches
+
+// launchers: one switch on the plan's schedule per dtype (attn_launch.cuh), and below it one function per kernel family,
+// each instantiated in the translation unit of its family and dtype (so they compile in parallel)
+typedef __bf16 bf16_t;
+typedef _Float16 f16_t;
+template <typename T> int launch_attn_fwd(const AttnPlan& pl, const HstuAttnParams& p, hipStream_t st);
+template <typename T> int launch_attn_bwd(const AttnPlan& pl, const HstuAttnBwdParams& bp, hipStream_t st);
+template <typename T> int launch_fwd_bias(const AttnPlan& pl, const HstuAttnParams& p, hipStream_t st);        // attn_bias_*.hip
+template <typename T> int launch_bwd_bias(const AttnPlan& pl, const HstuAttnBwdParams& bp, hipStream_t st);    // (general and folded)
+template <typename T> int launch_fwd_solo(const AttnPlan& pl, const HstuAttnParams& p, hipStream_t st);        // attn_solo_*.hip
+template <typename T> int launch_bwd_solo(const AttnPlan& pl, const HstuAttnBwdParams& bp, hipStream_t st);
+template <typename T> int launch_fwd_solo_bias(const AttnPlan& pl, const HstuAttnParams& p, hipStream_t st);
+template <typename T> int launch_bwd_solo_bias(const AttnPlan& pl, const HstuAttnBwdParams& bp, hipStream_t st);
+template <typename T> int launch_bwd_fold(const AttnPlan& pl, const HstuAttnBwdParams& bp, hipStream_t st);    // attn_fold_*.hip (and quad)
+template <typename T> int launch_bwd_long(const AttnPlan& pl, const HstuAttnBwdParams& bp, hipStream_t st);    // attn_long_*.hip
+// (attn_launch.cuh holds the schedule switch AND the bias launchers it calls: only attn_bias_*.hip instantiate the latter)
+#define HSTU_ATTN_BIAS_EXTERN(T)                                                               \
+  extern template int launch_fwd_bias<T>(const AttnPlan&, const HstuAttnParams&, hipStream_t); \
+  extern template int launch_bwd_bias<T>(const AttnPlan&, const HstuAttnBwdParams&, hipStream_t);
+HSTU_ATTN_BIAS_EXTERN(bf16_t) HSTU_ATTN_BIAS_EXTERN(f16_t) HSTU_ATTN_BIAS_EXTERN(float)
+#undef HSTU_ATTN_BIAS_EXTERN
+// sums the per-workgroup bias-gradient rows of the plan's workspace into dpos_w / dts_w (two fixed-order stages)
+int launch_bias_grad_reduce(const AttnPlan& pl, void* workspace, int npos, float* dpos_w, float* dts_w, hipStream_t st);
 
 // compute units of the CURRENT device (cached per device: a host may hold devices of different sizes)
 inline int cu_count() {
@@ -82,12 +93,22 @@ inline int cu_count() {
 }
 inline int pad_head_dim(int d) { return d <= 32 ? 32 : (d <= 64 ? 64 : (d <= 128 ? 128 : 0)); }
 constexpr int kLdsBudget = 160 * 1024;
+// more than 64 KiB of dynamic LDS has to be asked for, per kernel
+inline int reserve_lds(const void* kern, int smem, const char* who) {
+  if (smem <= 64 * 1024) return HSTU_OK;
+  hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+  return e == hipSuccess ? HSTU_OK : set_error(HSTU_ELAUNCH, "%s: cannot reserve %d bytes of LDS: %s", who, smem, hipGetErrorString(e));
+}
 // bytes of the bias tables a workgroup stages in LDS: pos_w (2N-1 floats), ts_w (nb+1 floats), N int64 timestamps,
 // their int32 offsets
 inline int bias_table_bytes(int max_seq_len, int num_buckets) {
   return 128 /* zeros in front of the position table: see stage_bias_tables */ +
          ((2 * max_seq_len * 4 + 15) / 16 + ((num_buckets + 1) * 4 + 15) / 16 + (max_seq_len * 8 + 15) / 16) * 16 +
          (2 * ((max_seq_len + 32 + 3) / 4 * 4) * 4 + 8 * 4 + 15) / 16 * 16;   // + int32 offsets and their copy shifted by one (padded), one range flag per wave
+}
+inline int zero_workspace(void* ptr, size_t bytes, hipStream_t st) {
+  hipError_t e = bytes ? hipMemsetAsync(ptr, 0, bytes, st) : hipSuccess;
+  return e == hipSuccess ? HSTU_OK : set_error(HSTU_ELAUNCH, "hstu_attn_bwd: workspace memset failed: %s", hipGetErrorString(e));
 }
 constexpr int kDqScratchBytes = 8 * 4096;   // general backward, several key blocks: one [32 q][32 d] fp32 tile per wave
 

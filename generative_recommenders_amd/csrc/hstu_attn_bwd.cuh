@@ -32,35 +32,6 @@
 
 namespace hstu {
 
-constexpr int kBwdThreads = 512;
-constexpr int kBwdWaves = 8;
-
-template <typename T, int DQK, int DV>
-struct BwdCfg {
-  static constexpr int EB = Elem<T>::kBytes;
-  static constexpr int EPU = 16 / EB;
-  static constexpr int UPR_K = DQK * EB / 16;
-  static constexpr int UPR_V = DV * EB / 16;
-  static constexpr int KT = 32 * DQK * EB;
-  static constexpr int VT = 32 * DV * EB;
-  static constexpr int PAIR = KT + VT;            // K+V tile, also Q+dO stage
-  static constexpr int DSROW = (EB == 2) ? 72 : 144;  // padded [key][32 q] row of the dS buffer
-  static constexpr int DSBUF = 32 * DSROW;
-  static constexpr int KGQ = DQK / 16;
-  static constexpr int KGV = DV / 16;
-  static constexpr int DBQ = DQK / 32;
-  static constexpr int DBV = DV / 32;
-  static constexpr int NQU = (32 * UPR_K + kBwdThreads - 1) / kBwdThreads;
-  static constexpr int NOU = (32 * UPR_V + kBwdThreads - 1) / kBwdThreads;
-  static constexpr int smem_bytes(int nw, int extra = 0) { return nw * PAIR + PAIR + 2 * nw * DSBUF + extra; }
-  // at most 7 key tiles per block: the 8th wave never owns a tile, so every step has a
-  // helper wave for the dQ GEMM of the previous step
-  static constexpr int max_tiles(int lds_budget) {
-    int nw = (lds_budget - PAIR) / (PAIR + 2 * DSBUF);
-    return nw > kBwdWaves - 1 ? kBwdWaves - 1 : nw;
-  }
-};
-
 // Column fragment from the (unswizzled, padded) dS buffer: slot j<4 -> buf[rowA+j][n32],
 // slot j>=4 -> buf[rowB+j-4][n32].
 template <typename T, int ROWB>

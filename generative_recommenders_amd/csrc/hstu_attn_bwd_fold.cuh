@@ -38,15 +38,6 @@
 
 namespace hstu {
 
-template <typename T, int DQK, int DV>
-struct FoldCfg {
-  using B = BwdCfg<T, DQK, DV>;
-  static constexpr int DSB = 32 * 64;                    // [32 keys][32 q] 16-bit tile, 64-byte rows
-  static constexpr int kMaxTiles = kBwdWaves - 1;
-  // all kMaxTiles K/V slots are always allocated (the dQ GEMM reads every slot, used or not)
-  static constexpr int smem_bytes() { return (kMaxTiles + 2) * B::PAIR + kBwdWaves * DSB; }
-};
-
 // LDS-DMA of one [32][D] tile (as tile_dma in hstu_attn_fwd.cuh), issued through inline asm.  Why asm: for the
 // builtin, hipcc's waitcnt pass assumes that ANY later LDS read may alias the tile in flight and puts an
 // s_waitcnt vmcnt(0) in front of it -- here that is the first read of the dQ GEMM, which only touches K tiles and

@@ -29,22 +29,6 @@
 
 namespace hstu {
 
-#ifndef LONG_NW
-#define LONG_NW 7
-#endif
-#ifndef LONG_STAGES
-#define LONG_STAGES 3
-#endif
-constexpr int kLongNW = LONG_NW;            // key tiles (owner waves) per block of the dK / dV kernel
-constexpr int kLongStages = LONG_STAGES;    // its Q / dO ring
-static_assert(kLongNW <= kBwdWaves && kLongStages >= 2 && (kLongNW + kLongStages) * 16 <= 160, "LDS");
-
-template <typename T, int D>
-struct LongCfg {
-  using B = BwdCfg<T, D, D>;
-  static constexpr int smem_dkv() { return (kLongNW + kLongStages) * B::PAIR; }
-};
-
 // -------------------------------------------------------------------------------------------------------------------------------
 // dK / dV
 // -------------------------------------------------------------------------------------------------------------------------------
@@ -395,33 +379,22 @@ __global__ __launch_bounds__(kFwdThreads, 2) void hstu_attn_bwd_dq_kernel(const 
 
 // -------------------------------------------------------------------------------------------------------------------------------
 template <typename T, int D>
-static int launch_bwd_long_inst(const HstuAttnBwdParams& bp, hipStream_t st) {
-  const HstuAttnParams& p = bp.fwd;
-  const int tmax = (p.max_seq_len + 31) / 32;
-  const int groups = (p.batch * p.heads + 7) / 8;
+static int launch_bwd_long_inst(const AttnPlan& pl, const HstuAttnBwdParams& bp, hipStream_t st) {
+  const AttnLaunch &dkv = pl.launch[0], &dq = pl.launch[1];
   {
-    const int nkb = (tmax + kLongNW - 1) / kLongNW;
-    const int smem = LongCfg<T, D>::smem_dkv();
-    auto kern = p.contextual_seq_len > 0 ? hstu_attn_bwd_dkv_kernel<T, D, true> : hstu_attn_bwd_dkv_kernel<T, D, false>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) return set_error(HSTU_ELAUNCH, "hstu_attn_bwd(long): cannot reserve %d bytes of LDS: %s", smem, hipGetErrorString(e));
-    hipLaunchKernelGGL(kern, dim3(groups * 8 * nkb), dim3(kBwdThreads), smem, st, bp, nkb);
+    auto kern = pl.contextual ? hstu_attn_bwd_dkv_kernel<T, D, true> : hstu_attn_bwd_dkv_kernel<T, D, false>;
+    if (int e = reserve_lds((const void*)kern, dkv.smem, "hstu_attn_bwd(long)")) return e;
+    hipLaunchKernelGGL(kern, dim3(dkv.grid), dim3(kBwdThreads), dkv.smem, st, bp, pl.nkb);
     if (int rc = check_launch("hstu_attn_bwd(long, dk/dv)")) return rc;
   }
-  {
-    using C = FwdCfg<T, D, D>;
-    const int nqb = (p.max_seq_len + kFwdRowsPerBlock - 1) / kFwdRowsPerBlock;
-    auto kern = p.contextual_seq_len > 0 ? hstu_attn_bwd_dq_kernel<T, D, true> : hstu_attn_bwd_dq_kernel<T, D, false>;
-    hipLaunchKernelGGL(kern, dim3(groups * 8 * nqb), dim3(kFwdThreads), C::SMEM, st, bp, nqb);
-    return check_launch("hstu_attn_bwd(long, dq)");
-  }
+  auto kern = pl.contextual ? hstu_attn_bwd_dq_kernel<T, D, true> : hstu_attn_bwd_dq_kernel<T, D, false>;
+  hipLaunchKernelGGL(kern, dim3(dq.grid), dim3(kFwdThreads), dq.smem, st, bp, pl.nqb);
+  return check_launch("hstu_attn_bwd(long, dq)");
 }
 
 template <typename T>
-static int launch_bwd_long_dtype(const HstuAttnBwdParams& bp, hipStream_t st) {
-  if (bp.fwd.dqk == 128) return launch_bwd_long_inst<T, 128>(bp, st);
-  if (bp.fwd.dqk == 64) return launch_bwd_long_inst<T, 64>(bp, st);
-  return set_error(HSTU_EUNSUPPORTED, "hstu_attn_bwd(long): head dim %d not instantiated", bp.fwd.dqk);
+int launch_bwd_long(const AttnPlan& pl, const HstuAttnBwdParams& bp, hipStream_t st) {
+  return pl.a == 128 ? launch_bwd_long_inst<T, 128>(pl, bp, st) : launch_bwd_long_inst<T, 64>(pl, bp, st);
 }
 
 }  // namespace hstu

@@ -23,18 +23,6 @@
 
 namespace hstu {
 
-constexpr int kQuadWaves = 4;
-constexpr int kQuadThreads = 256;
-
-template <typename T, int D>
-struct QuadCfg {
-  using B = BwdCfg<T, D, D>;
-  static constexpr int DSB = 32 * 64;                 // [32 keys][32 q] 16-bit dS' tile
-  static constexpr int kMaxTiles = 7;
-  // 7 K/V pairs + one Q/dO stage + 7 dS' tiles
-  static constexpr int smem_bytes() { return kMaxTiles * B::PAIR + B::PAIR + kMaxTiles * DSB; }
-};
-
 template <typename T, int D>
 HSTU_DEV void quad_tile_dma(char* tile, const char* base, int64_t row_stride_bytes, int row0, int len, int wave, int lane, bool fast = false) {
   constexpr int UPR = D * Elem<T>::kBytes / 16;

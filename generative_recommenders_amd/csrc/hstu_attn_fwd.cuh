@@ -19,41 +19,16 @@
 // counted s_waitcnt vmcnt; three workgroups per CU (165 VGPRs).  (2 stages when a stage exceeds 16 KiB: FwdCfg.)
 // HSTU has no softmax, so there is no running max / rescale: tiles are independent.
 #pragma once
-#include "hstu_common.cuh"
+#include "attn_cfg.cuh"
 
 namespace hstu {
 
-constexpr int kFwdThreads = 256;
 #ifndef HSTU_FWD_MIN_WAVES
 #define HSTU_FWD_MIN_WAVES 2
 #endif
 // (round 6: the measured-and-lost switches of this kernel -- K tiles three ahead behind a second barrier, first tiles requested in front of
 // the Q rows, wave priority by phase, the conflict-free park of the output tile, the builtin form of the DMA instruction -- left the
 // source; the version that carried them: docs/experiments/r06_hstu_attn_fwd_with_switches.cuh.txt, results docs/EXPERIMENTS.md A.3, R5.7)
-constexpr int kFwdRowsPerBlock = 128;
-
-template <typename T, int DQK, int DV>
-struct FwdCfg {
-  static constexpr int EB = Elem<T>::kBytes;
-  static constexpr int EPU = 16 / EB;            // elements per 16-byte unit
-  static constexpr int UPR_K = DQK * EB / 16;    // units per K row
-  static constexpr int UPR_V = DV * EB / 16;
-  static constexpr int KT = 32 * DQK * EB;       // bytes of a 32-row K tile
-  static constexpr int VT = 32 * DV * EB;
-  static constexpr int STAGE = KT + VT;
-  static constexpr int KG = DQK / 16;            // 16-wide contraction groups of QK^T
-  static constexpr int DB = DV / 32;             // 32-wide output blocks
-  static constexpr int NKU = (32 * UPR_K + kFwdThreads - 1) / kFwdThreads;  // staged units / thread
-  static constexpr int NVU = (32 * UPR_V + kFwdThreads - 1) / kFwdThreads;
-  // K/V ring filled by LDS-DMA.  Counted vmcnt waits need every wave to issue the same number of
-  // DMA instructions per tile (whole multiples of the 4 waves); otherwise depth 2 with full drains.
-  static constexpr int NCH_K = 32 * UPR_K / 64, NCH_V = 32 * UPR_V / 64;
-  static constexpr bool COUNTED = (NCH_K % 4 == 0) && (NCH_V % 4 == 0);
-  static constexpr int PER_TILE = NCH_K / 4 + NCH_V / 4;      // DMA instructions per wave per tile
-  static constexpr int NS = (COUNTED && STAGE <= 16384) ? 3 : 2;  // ring depth (= tiles in flight + 1)
-  static constexpr int SMEM = NS * STAGE;
-};
-
 // Cooperative global -> register load of one [32][D] tile and the matching register -> LDS
 // write.  The loads are UNCONDITIONAL on clamped (always valid) addresses so that nothing
 // consumes the loaded registers until tile_lds_write: the global loads stay in flight across

@@ -13,20 +13,6 @@
 
 namespace hstu {
 
-constexpr int kSoloWaves = 4;
-constexpr int kSoloThreads = 256;
-constexpr int kSoloD = 32;          // instantiated head dim (16-bit: 64-byte rows, 2 KiB tiles)
-constexpr int kSoloMaxLen = 64;
-
-template <typename T>
-struct SoloCfg {
-  static constexpr int TILE = 32 * kSoloD * Elem<T>::kBytes;      // 2048
-  static constexpr int UPR = kSoloD * Elem<T>::kBytes / 16;        // 4
-  // per wave: K, V, Q (2 tiles each; forward: 12 KiB -> 3 workgroups per CU) + dO and 2 dS' tiles (backward: 20 KiB)
-  static constexpr int bwd_slice(int tpt = 2) { return tpt * (4 * TILE + 32 * 64); }
-  static constexpr int fwd_slice(int tpt = 2) { return 3 * tpt * TILE; }   // the output tile is parked over the query tile it came from
-};
-
 // [rows of one tensor] -> this wave's LDS tiles, zero filled: 2 units (16 B) per lane and tile.  Two halves: the
 // loads (issue) and the LDS writes (commit), so that all the loads of a problem are in flight before the first write.
 template <typename T, int TPT = 2>
@@ -122,7 +108,6 @@ HSTU_DEV void solo_fwd_issue(const HstuAttnParams& p, const SoloProb& pr, u32x4 
 // 512 bytes per half tile (8 per lane), half tile (pair, h8) at ((pair * 2 + h8) * 512), pair = i (i + 1) / 2 + t for
 // query tile i, key tile t <= i.  Two layouts, each what its consumer's registers hold: forward S^T (lane = query,
 // registers = keys), backward S (lane = key, registers = queries: the layout of fold_pair_x's byte cache).
-constexpr int kSoloBucketBytes = 3 * 1024;
 template <bool BWD>
 HSTU_DEV void solo_bucket_bytes(const BiasCtx& bc, char* bcache, int len, int wave, int lane, int nwaves = kSoloWaves) {
   const int n32 = lane & 31, hf = lane >> 5;
@@ -591,9 +576,6 @@ __global__ __launch_bounds__(kSoloThreads) __attribute__((amdgpu_waves_per_eu(TP
 // TPT = 1: the launch that takes the (user, head) problems of <= 32 rows only -- slices of one tile per tensor (10 KiB per wave instead of
 // 20), half the accumulators and staging registers (128 instead of 213): four workgroups per CU instead of two (the other launch takes
 // the longer users)
-#ifndef SOLO_BWD_SHORT_WAVES
-#define SOLO_BWD_SHORT_WAVES 4
-#endif
 template <typename T, int TPT>
 __global__ __launch_bounds__(kSoloThreads) __attribute__((amdgpu_waves_per_eu(TPT == 1 ? SOLO_BWD_SHORT_WAVES : 2, TPT == 1 ? SOLO_BWD_SHORT_WAVES : 2)))
 void hstu_attn_bwd_solo_kernel(const HstuAttnBwdParams bp, int len_lo, int len_hi) {

@@ -250,6 +250,89 @@ def test_short_sequence_bias_kernels(dtype, H, d, n, B, with_ts):
         _close(ts_w.grad, rts, 2e-3, 1e-4, f"dts_w[{tag} solo]")
 
 
+_GUARD = 4 << 20
+
+
+@pytest.mark.parametrize("dtype,d,n,B,H,bias,det,name", [
+    (torch.bfloat16, 16, 61, 8, 4, True, 0, "hstu_attn_bwd_solo_bias_kernel<bf16>"),
+    # one head: both length classes write a partial row per user (130 + 130 rows) -- more than users x heads rounded up
+    (torch.bfloat16, 16, 61, 130, 1, True, 0, "hstu_attn_bwd_solo_bias_kernel<bf16>"),
+    (torch.bfloat16, 64, 100, 3, 2, True, 0, "hstu_attn_bwd_fold_bias_kernel<bf16,64>"),
+    (torch.bfloat16, 32, 100, 3, 2, True, 0, "hstu_attn_bwd_kernel<bf16,32,32,bias>"),
+    (torch.float32, 128, 256, 3, 2, False, 0, "hstu_attn_bwd_kernel<f32,128,128>"),
+    (torch.float32, 128, 256, 3, 2, False, 1, "hstu_attn_bwd_kernel<f32,128,128>")])
+def test_backward_stays_inside_its_workspace(dtype, d, n, B, H, bias, det, name):
+    """Every schedule that writes a workspace, called through the C ABI with hstu_attn_bwd_workspace_bytes() bytes at the
+    head of ONE allocation and 4 MiB of a byte pattern behind them: the pattern survives the backward (memsets, partial
+    rows, the user counter, the reduce's chunk sums and the dq accumulator all lie inside the reported size), the
+    gradients match the fp64 oracle, and the kernel is the one the case is about."""
+    import ctypes as C
+
+    from generative_recommenders_amd import _lib as L
+    from generative_recommenders_amd.ops import _launch
+    from test_configs_gpu import _timestamps_off_bucket_boundaries
+
+    m = _mods()
+    torch.manual_seed(n + B)
+    rng = np.random.default_rng(n + B + H)
+    lengths = rng.integers(0, n + 1, size=B)
+    lengths[:3] = [n, 1, min(32, n)]                       # (both sides of 32: the length classes of the short-sequence kernels)
+    lengths[B - 1] = min(33, n)
+    off = O.complete_cumsum(lengths.astype(np.int64))
+    Lt = int(off[-1])
+    mk = lambda s: torch.from_numpy(rng.standard_normal((Lt, H, d)) * s).to(dtype)
+    q, k, v, g = mk(0.3), mk(0.3), mk(0.3), mk(1.0)
+    qd, kd, vd, gd = (t.to(DEV) for t in (q, k, v, g))
+    dq, dk, dv = torch.empty_like(qd), torch.empty_like(kd), torch.empty_like(vd)
+    offd = _launch._idx(torch.from_numpy(off).to(DEV))
+    bp = L.HstuAttnBwdParams()
+    _launch._fill_attn_params(bp.fwd, qd, kd, vd, None, offd, None, n, 1.0, 1.0 / n, 0, 0, 0, 0)
+    if bias:
+        ts = _timestamps_off_bucket_boundaries(rng, B, n)
+        mod = m.RelativeBucketedTimeAndPositionBasedBias(n, 128).to(DEV)
+        with torch.no_grad():
+            for prm in mod.parameters():
+                prm.normal_(0, 0.05)
+        pos_w, ts_w, num_buckets, bucket_div = mod.bias_params()
+        pos32, ts32 = pos_w.detach().float().contiguous(), ts_w.detach().float().contiguous()
+        tsd = torch.from_numpy(ts).to(DEV)
+        m._fill_bias(bp.fwd, pos32, ts32, tsd, num_buckets, bucket_div)
+        dpos, dts = torch.zeros_like(pos32), torch.zeros_like(ts32)
+        bp.dpos_w, bp.dts_w = dpos.data_ptr(), dts.data_ptr()
+    bp.dout, bp.dq, bp.dk, bp.dv = gd.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+    bp.do_row_stride, bp.do_head_stride = gd.stride(0), gd.stride(1)
+    bp.dq_row_stride, bp.dq_head_stride = dq.stride(0), dq.stride(1)
+    bp.dk_row_stride, bp.dk_head_stride = dk.stride(0), dk.stride(1)
+    bp.dv_row_stride, bp.dv_head_stride = dv.stride(0), dv.stride(1)
+    bp.total_rows = Lt
+    bp.deterministic = det
+    lib = L.lib()
+    buf = C.create_string_buffer(128)
+    L.check(lib.hstu_attn_bwd_kernel_name(C.byref(bp), buf, 128))
+    assert buf.value.decode() == name
+    ws_bytes = lib.hstu_attn_bwd_workspace_bytes(C.byref(bp))
+    assert ws_bytes > 0
+    ws = torch.full((ws_bytes + _GUARD,), 0xA5, dtype=torch.uint8, device=DEV)
+    bp.workspace = ws.data_ptr()
+    with torch.cuda.device(qd.device):
+        L.check(lib.hstu_attn_bwd(C.byref(bp), L.current_stream_ptr(qd.device)))
+    torch.cuda.synchronize()
+    assert bool((ws[ws_bytes:] == 0xA5).all()), "the backward wrote past hstu_attn_bwd_workspace_bytes()"
+    q3, k3, v3, g3 = (t.double().numpy() for t in (q, k, v, g))
+    tol = (1e-3, 1e-5) if dtype == torch.float32 else (3e-2, 6e-3)
+    if bias:
+        pw, tw = pos32.double().cpu().numpy(), ts32.double().cpu().numpy()
+        rq, rk, rv, rpos, rts = O.rel_bias_attention_bwd(n, g3, q3, k3, v3, off, ts, pw, tw)
+        tag = f"{str(dtype).replace('torch.', '')} guard band"
+        _close(dpos, rpos, 2e-3, 1e-4, f"dpos_w[{tag}]")
+        _close(dts, rts, 2e-3, 1e-4, f"dts_w[{tag}]")
+    else:
+        rq, rk, rv = O.hstu_mha_bwd(n, 1.0, g3, q3, k3, v3, off)
+    _close(dq, rq, *tol, "dq")
+    _close(dk, rk, *tol, "dk")
+    _close(dv, rv, *tol, "dv")
+
+
 def test_research_layer_forward_backward_runs_and_matches_composition():
     """SequentialTransductionUnitJagged on the fused kernels == the same math composed from the
     oracle pieces (LN without affine -> uvqk -> SiLU on all -> bias attention -> u * LN(attn) -> Linear + x)."""

@@ -10,19 +10,17 @@ wait
 cat > build_trace/stubs.cpp <<'EOS'
 #include "../capi_internal.h"
 namespace hstu {
-int launch_attn_fwd_f16(const HstuAttnParams&, hipStream_t) { return -2; }
-int launch_attn_fwd_f32(const HstuAttnParams&, hipStream_t) { return -2; }
-int launch_attn_bwd_f16(const HstuAttnBwdParams&, hipStream_t) { return -2; }
-int launch_attn_bwd_f32(const HstuAttnBwdParams&, hipStream_t) { return -2; }
-int attn_bwd_tiles_f16(int, int, int, int) { return 0; }
-int attn_bwd_tiles_f32(int, int, int, int) { return 0; }
-int launch_attn_fwd_bias_f16(const HstuAttnParams&, hipStream_t) { return -2; }
-int launch_attn_fwd_bias_f32(const HstuAttnParams&, hipStream_t) { return -2; }
-int launch_attn_bwd_bias_f16(const HstuAttnBwdParams&, hipStream_t) { return -2; }
-int launch_attn_bwd_bias_f32(const HstuAttnBwdParams&, hipStream_t) { return -2; }
-int launch_attn_bwd_fold_f16(const HstuAttnBwdParams&, hipStream_t) { return -2; }
-int launch_attn_fwd_solo_f16(const HstuAttnParams&, hipStream_t) { return -2; }
-int launch_attn_bwd_solo_f16(const HstuAttnBwdParams&, hipStream_t) { return -2; }
+// the launchers of the units this build leaves out
+#define FWD(NAME) template <typename T> int NAME(const AttnPlan&, const HstuAttnParams&, hipStream_t) { return -2; }
+#define BWD(NAME) template <typename T> int NAME(const AttnPlan&, const HstuAttnBwdParams&, hipStream_t) { return -2; }
+FWD(launch_attn_fwd) BWD(launch_attn_bwd) FWD(launch_fwd_bias) BWD(launch_bwd_bias) FWD(launch_fwd_solo) BWD(launch_bwd_solo)
+FWD(launch_fwd_solo_bias) BWD(launch_bwd_solo_bias) BWD(launch_bwd_fold) BWD(launch_bwd_long)
+#define FWD_INST(NAME, T) template int NAME<T>(const AttnPlan&, const HstuAttnParams&, hipStream_t);
+#define BWD_INST(NAME, T) template int NAME<T>(const AttnPlan&, const HstuAttnBwdParams&, hipStream_t);
+FWD_INST(launch_attn_fwd, f16_t) FWD_INST(launch_attn_fwd, float) BWD_INST(launch_attn_bwd, f16_t) BWD_INST(launch_attn_bwd, float)
+FWD_INST(launch_fwd_bias, f16_t) FWD_INST(launch_fwd_bias, float) BWD_INST(launch_bwd_bias, f16_t) BWD_INST(launch_bwd_bias, float)
+FWD_INST(launch_fwd_solo, f16_t) BWD_INST(launch_bwd_solo, f16_t) FWD_INST(launch_fwd_solo_bias, f16_t) BWD_INST(launch_bwd_solo_bias, f16_t)
+BWD_INST(launch_bwd_fold, f16_t) BWD_INST(launch_bwd_long, f16_t) BWD_INST(launch_bwd_long, bf16_t)
 }
 EOS
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I. -I../../include -c build_trace/stubs.cpp -o build_trace/stubs.o
