@@ -155,6 +155,42 @@ static int column_sum_groups(int64_t rows, int cols) {
   return g < 1 ? 1 : (int)g;
 }
 
+// ---- finish of the row-pass backward kernels (multitask head, timestamp LayerNorm; capi_internal.h): a different fixed
+// order from column_sum_finish_kernel's -- thread (r, cc) adds partial rows r, r + 16, .. of column cc into ONE running
+// sum (64-byte segments per row), then the 16 sums are added in index order
+struct ColSegments {
+  ColSegment s[4];
+};
+
+__global__ __launch_bounds__(256) void partial_col_sums_kernel(const float* partial, int nparts, int64_t pstride, const ColSegments seg) {
+  __shared__ float red[16][17];
+  const int cc = threadIdx.x & 15, r = threadIdx.x >> 4;
+  const int64_t col = (int64_t)blockIdx.x * 16 + cc;
+  float s = 0.f;
+  if (col < pstride)
+    for (int i = r; i < nparts; i += 16) s += partial[(int64_t)i * pstride + col];
+  red[r][cc] = s;
+  __syncthreads();
+  if (r == 0 && col < pstride) {
+    float tot = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) tot += red[k][cc];
+    int64_t c = col;   // the column inside segment j, once the lengths of the segments before it are taken off
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (c >= 0 && c < seg.s[j].len) seg.s[j].out[c] = tot;
+      c -= seg.s[j].len;
+    }
+  }
+}
+
+int launch_partial_col_sums(const float* partial, int nparts, int64_t pstride, const ColSegment (&segs)[4], const char* who,
+                            hipStream_t st) {
+  const ColSegments seg{{segs[0], segs[1], segs[2], segs[3]}};
+  hipLaunchKernelGGL(partial_col_sums_kernel, dim3((unsigned)((pstride + 15) / 16)), dim3(256), 0, st, partial, nparts, pstride, seg);
+  return check_launch(who);
+}
+
 // ---- calibration streams
 template <int DUMMY>
 __global__ __launch_bounds__(256) void calib_mfma_kernel(int iters, float* sink) {

@@ -30,9 +30,9 @@ static int validate_attn(const HstuAttnParams& p, const char* who) {
   if (!p.q || !p.k || !p.v || !p.seq_offsets) return set_error(HSTU_EINVAL, "%s: q, k, v and seq_offsets must be non-NULL", who);
   if (p.batch < 0 || p.heads <= 0) return set_error(HSTU_EINVAL, "%s: bad batch/heads", who);
   if (p.max_seq_len <= 0) return set_error(HSTU_EINVAL, "%s: max_seq_len must be larger than 0", who);
-  if (p.dtype != HSTU_DTYPE_BF16 && p.dtype != HSTU_DTYPE_F16 && p.dtype != HSTU_DTYPE_F32)
+  if (!is_float_dtype(p.dtype))
     return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32", who);
-  const int eb = p.dtype == HSTU_DTYPE_F32 ? 4 : 2;
+  const int eb = dtype_bytes(p.dtype);
   const int epu = 16 / eb;
   if (p.dqk <= 0 || p.dv <= 0 || p.dqk % epu || p.dv % epu)
     return set_error(HSTU_EINVAL, "%s: head dims (%d, %d) must be positive multiples of %d", who, p.dqk, p.dv, epu);
@@ -95,7 +95,7 @@ int hstu_attn_fwd(const HstuAttnParams* p, void* stream) {
   if (p->dtype == HSTU_DTYPE_FP8_E4M3) return attn_fwd_fp8(p, HstuFp8Descale{}, stream);   // every descale 1
   if (int e = validate_attn(*p, "hstu_attn_fwd")) return e;
   if (!p->out) return set_error(HSTU_EINVAL, "hstu_attn_fwd: out is NULL");
-  if (((p->o_row_stride | p->o_head_stride) * (p->dtype == HSTU_DTYPE_F32 ? 4 : 2)) % 16 || ((uintptr_t)p->out & 15))
+  if (((p->o_row_stride | p->o_head_stride) * dtype_bytes(p->dtype)) % 16 || ((uintptr_t)p->out & 15))
     return set_error(HSTU_EINVAL, "hstu_attn_fwd: out rows must be 16-byte aligned");
   if (p->batch == 0) return HSTU_OK;   // empty batch: nothing to launch (flash_common.cpp:548-551)
   const AttnPlan pl = plan_attn_fwd(*p);
@@ -148,7 +148,7 @@ int hstu_attn_bwd(const HstuAttnBwdParams* p, void* stream) {
   if (int e = validate_attn(p->fwd, "hstu_attn_bwd")) return e;
   if (p->fwd.delta_q != 0) return set_error(HSTU_EUNSUPPORTED, "hstu_attn_bwd: delta_q attention is forward-only (as in the reference)");
   if (!p->dout || !p->dq || !p->dk || !p->dv) return set_error(HSTU_EINVAL, "hstu_attn_bwd: dout, dq, dk, dv must be non-NULL");
-  const int eb = p->fwd.dtype == HSTU_DTYPE_F32 ? 4 : 2;
+  const int eb = dtype_bytes(p->fwd.dtype);
   const int64_t strides[] = {p->do_row_stride, p->do_head_stride, p->dq_row_stride, p->dq_head_stride,
                              p->dk_row_stride, p->dk_head_stride, p->dv_row_stride, p->dv_head_stride};
   for (int64_t s : strides)
@@ -179,7 +179,7 @@ int hstu_jagged_quantize_fp8(const void* x, int64_t x_row_stride, int64_t x_head
                              void* stream) {
   if (!x || !x8 || !descale || !seq_offsets) return set_error(HSTU_EINVAL, "hstu_jagged_quantize_fp8: x, x8, descale and seq_offsets must be non-NULL");
   if (batch < 0 || heads <= 0 || dim <= 0) return set_error(HSTU_EINVAL, "hstu_jagged_quantize_fp8: bad batch / heads / dim");
-  if (dtype != HSTU_DTYPE_BF16 && dtype != HSTU_DTYPE_F16 && dtype != HSTU_DTYPE_F32)
+  if (!is_float_dtype(dtype))
     return set_error(HSTU_EINVAL, "hstu_jagged_quantize_fp8: x must be bf16, fp16 or fp32");
   if (index_dtype != HSTU_INDEX_I32 && index_dtype != HSTU_INDEX_I64) return set_error(HSTU_EINVAL, "hstu_jagged_quantize_fp8: bad index dtype");
   if (batch == 0) return HSTU_OK;
@@ -189,7 +189,7 @@ int hstu_jagged_quantize_fp8(const void* x, int64_t x_row_stride, int64_t x_head
 
 // shared checks of the two jagged_dense_bmm entry points (shape and type codes first: they need no pointer)
 static int validate_bmm_shape(const char* who, int64_t total_rows, int32_t batch, int32_t k, int32_t n, int dtype, int index_dtype) {
-  if (dtype != HSTU_DTYPE_BF16 && dtype != HSTU_DTYPE_F16 && dtype != HSTU_DTYPE_F32)
+  if (!is_float_dtype(dtype))
     return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32 (got code %d)", who, dtype);
   if (index_dtype != HSTU_INDEX_I32 && index_dtype != HSTU_INDEX_I64)
     return set_error(HSTU_EINVAL, "%s: seq_offsets must be int32 or int64 (got code %d)", who, index_dtype);
@@ -219,7 +219,7 @@ int hstu_jagged_dense_bmm_fwd(const void* jagged, int64_t jagged_row_stride, con
   if (batch == 0 || total_rows == 0) return HSTU_OK;
   if (!jagged || !dense || !out || !seq_offsets || !workspace)
     return set_error(HSTU_EINVAL, "%s: jagged, dense, out, seq_offsets and workspace must be non-NULL", who);
-  const int eb = dtype == HSTU_DTYPE_F32 ? 4 : 2;
+  const int eb = dtype_bytes(dtype);
   if (dense_n_stride != 1 && dense_k_stride != 1)
     return set_error(HSTU_EINVAL, "%s: dense needs a unit stride along K or N (got %lld, %lld)", who, (long long)dense_k_stride,
                      (long long)dense_n_stride);
@@ -242,7 +242,7 @@ int hstu_jagged_dense_bmm_wgrad(const void* jagged, int64_t jagged_row_stride, c
   if (batch == 0) return HSTU_OK;
   if (!d_dense || !seq_offsets || (total_rows > 0 && (!jagged || !d_out)))
     return set_error(HSTU_EINVAL, "%s: jagged, d_out, d_dense and seq_offsets must be non-NULL", who);
-  const int eb = dtype == HSTU_DTYPE_F32 ? 4 : 2;
+  const int eb = dtype_bytes(dtype);
   if ((total_rows > 0 && (jagged_row_stride < k || d_out_row_stride < n)) || d_dense_k_stride < n)
     return set_error(HSTU_EINVAL, "%s: a row stride is smaller than a row", who);
   if ((total_rows > 0 && (!bmm_aligned(eb, jagged, {jagged_row_stride}) || !bmm_aligned(eb, d_out, {d_out_row_stride}))) ||
@@ -259,11 +259,11 @@ int hstu_mips_topk(const void* queries, int64_t q_row_stride, const void* items,
                    int32_t* out_indices, void* workspace, int32_t batch, int32_t num_items, int32_t dim, int32_t k, int dtype,
                    void* stream) {
   const char* who = "hstu_mips_topk";
-  if (dtype != HSTU_DTYPE_BF16 && dtype != HSTU_DTYPE_F16 && dtype != HSTU_DTYPE_F32)
+  if (!is_float_dtype(dtype))
     return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32 (got code %d)", who, dtype);
   if (batch < 0) return set_error(HSTU_EINVAL, "%s: negative batch", who);
   if (num_items <= 0 || dim <= 0) return set_error(HSTU_EINVAL, "%s: num_items and dim must be positive (got %d, %d)", who, num_items, dim);
-  const int eb = dtype == HSTU_DTYPE_F32 ? 4 : 2, epu = 16 / eb;
+  const int eb = dtype_bytes(dtype), epu = 16 / eb;
   if (dim % epu) return set_error(HSTU_EINVAL, "%s: dim (%d) must be a multiple of %d elements (16 bytes); zero-pad it", who, dim, epu);
   if (dim > kMipsTopkMaxDim) return set_error(HSTU_EINVAL, "%s: dim %d exceeds the limit of %d", who, dim, kMipsTopkMaxDim);
   if (k < 1 || k > num_items || k > kMipsTopkMaxK)
@@ -283,7 +283,7 @@ int hstu_mol_scores(const void* qc, const void* xc, const void* gq, const void* 
                     const void* b2, float* out, int32_t batch, int32_t num_items, int32_t pq, int32_t px, int32_t dim,
                     int32_t hidden, float inv_temperature, int combination, int dtype, void* stream) {
   const char* who = "hstu_mol_scores";
-  if (dtype != HSTU_DTYPE_BF16 && dtype != HSTU_DTYPE_F16 && dtype != HSTU_DTYPE_F32)
+  if (!is_float_dtype(dtype))
     return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32 (got code %d)", who, dtype);
   if (combination != HSTU_MOL_GLU_SILU && combination != HSTU_MOL_GLU_SILU_LN)
     return set_error(HSTU_EINVAL, "%s: combination must be HSTU_MOL_GLU_SILU or HSTU_MOL_GLU_SILU_LN (got %d)", who, combination);
@@ -298,7 +298,7 @@ int hstu_mol_scores(const void* qc, const void* xc, const void* gq, const void* 
   if (batch == 0 || num_items == 0) return HSTU_OK;
   if (!qc || !xc || !gq || !gi || !w1 || !b2 || !out || (hidden > 0 && (!b1 || !w2)))
     return set_error(HSTU_EINVAL, "%s: operands, weights and out must be non-NULL", who);
-  const int eb = dtype == HSTU_DTYPE_F32 ? 4 : 2;
+  const int eb = dtype_bytes(dtype);
   if ((((uintptr_t)qc | (uintptr_t)xc) & 15) || (((uintptr_t)gq | (uintptr_t)gi | (uintptr_t)w1 | (uintptr_t)b1 | (uintptr_t)w2 | (uintptr_t)b2) & (eb - 1)) ||
       ((uintptr_t)out & 3))
     return set_error(HSTU_EINVAL, "%s: qc and xc must be 16-byte aligned, the other operands element aligned", who);
@@ -310,7 +310,7 @@ int hstu_mol_scores(const void* qc, const void* xc, const void* gq, const void* 
 static int validate_multitask(const char* who, const void* x, int64_t x_rs, const void* dx, int64_t dx_rs, const void* ln_w,
                               const void* ln_b, int64_t rows, int32_t dim, int32_t tasks, int32_t nbin, int dtype,
                               std::initializer_list<const void*> f32_ptrs, const void* workspace, bool* vec) {
-  if (dtype != HSTU_DTYPE_BF16 && dtype != HSTU_DTYPE_F16 && dtype != HSTU_DTYPE_F32)
+  if (!is_float_dtype(dtype))
     return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32 (got code %d)", who, dtype);
   if (tasks < 1 || tasks > HSTU_MULTITASK_MAX_TASKS)
     return set_error(HSTU_EINVAL, "%s: num_tasks must be in [1, %d] (got %d)", who, HSTU_MULTITASK_MAX_TASKS, tasks);
@@ -318,7 +318,7 @@ static int validate_multitask(const char* who, const void* x, int64_t x_rs, cons
     return set_error(HSTU_EINVAL, "%s: num_binary must be in [0, num_tasks = %d] (got %d)", who, tasks, nbin);
   if (rows < 0) return set_error(HSTU_EINVAL, "%s: negative rows", who);
   if (dim <= 0) return set_error(HSTU_EINVAL, "%s: dim must be positive (got %d)", who, dim);
-  const int eb = dtype == HSTU_DTYPE_F32 ? 4 : 2, epu = 16 / eb;
+  const int eb = dtype_bytes(dtype), epu = 16 / eb;
   const uintptr_t bits = (uintptr_t)x | (uintptr_t)dx | (uintptr_t)ln_w | (uintptr_t)ln_b;
   if (bits & (eb - 1)) return set_error(HSTU_EINVAL, "%s: x, dx and the norm's weight and bias must be aligned to their element size (%d bytes)", who, eb);
   for (const void* p : f32_ptrs)
@@ -388,7 +388,7 @@ int hstu_multitask_head_bwd(const float* grad_loss, const float* grad_pred, cons
 // ---- jagged causal softmax attention ----------------------------------------------------------------------------------------
 // checks that need no pointer first (shape, type codes, ranges), then pointers, then alignment
 static int validate_softmax_attn(const char* who, const SoftmaxAttnArgs& a, int64_t total_rows, bool backward, bool* empty) {
-  if (a.dtype != HSTU_DTYPE_BF16 && a.dtype != HSTU_DTYPE_F16 && a.dtype != HSTU_DTYPE_F32)
+  if (!is_float_dtype(a.dtype))
     return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32 (got code %d)", who, a.dtype);
   if (a.index_dtype != HSTU_INDEX_I32 && a.index_dtype != HSTU_INDEX_I64)
     return set_error(HSTU_EINVAL, "%s: seq_offsets must be int32 or int64 (got code %d)", who, a.index_dtype);
@@ -396,7 +396,7 @@ static int validate_softmax_attn(const char* who, const SoftmaxAttnArgs& a, int6
   if (a.head_dim <= 0) return set_error(HSTU_EINVAL, "%s: head_dim must be positive (got %d)", who, a.head_dim);
   if (a.head_dim > HSTU_SOFTMAX_ATTN_MAX_HEAD_DIM)
     return set_error(HSTU_EUNSUPPORTED, "%s: head_dim %d exceeds the limit of %d", who, a.head_dim, HSTU_SOFTMAX_ATTN_MAX_HEAD_DIM);
-  const int eb = a.dtype == HSTU_DTYPE_F32 ? 4 : 2, epu = 16 / eb;
+  const int eb = dtype_bytes(a.dtype), epu = 16 / eb;
   if (a.head_dim % epu)
     return set_error(HSTU_EINVAL, "%s: head_dim (%d) must be a multiple of %d elements (16 bytes); zero-pad it", who, a.head_dim, epu);
   if (a.max_seq_len < 1) return set_error(HSTU_EINVAL, "%s: max_seq_len must be at least 1 (got %d)", who, a.max_seq_len);
@@ -421,7 +421,7 @@ static int validate_softmax_attn(const char* who, const SoftmaxAttnArgs& a, int6
 }
 
 int hstu_softmax_attn_supported(int dtype, int32_t head_dim, int32_t max_seq_len) {
-  if (dtype != HSTU_DTYPE_BF16 && dtype != HSTU_DTYPE_F16 && dtype != HSTU_DTYPE_F32) return 0;
+  if (!is_float_dtype(dtype)) return 0;
   return head_dim >= 1 && head_dim <= HSTU_SOFTMAX_ATTN_MAX_HEAD_DIM && max_seq_len >= 1 && max_seq_len <= HSTU_SOFTMAX_ATTN_MAX_SEQ_LEN;
 }
 

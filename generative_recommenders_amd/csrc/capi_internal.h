@@ -99,6 +99,36 @@ inline int reserve_lds(const void* kern, int smem, const char* who) {
   hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
   return e == hipSuccess ? HSTU_OK : set_error(HSTU_ELAUNCH, "%s: cannot reserve %d bytes of LDS: %s", who, smem, hipGetErrorString(e));
 }
+inline int dtype_bytes(int dtype) { return dtype == HSTU_DTYPE_F32 ? 4 : 2; }
+inline bool is_float_dtype(int dtype) { return dtype == HSTU_DTYPE_BF16 || dtype == HSTU_DTYPE_F16 || dtype == HSTU_DTYPE_F32; }
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// ---- row-pass ops (device side: row_pass.cuh) ----
+// Grid of a row kernel with a grid-stride loop over `rows`, `rows_per_block` at a time: exactly the workgroups that are
+// resident at once (occupancy x CUs, shared among `cols` workgroup columns), so that every wave walks the same number of
+// rows and none starts late; at most max_blocks, at least 1.  Without an answer to the occupancy query: the row count's.
+template <typename K>
+inline int resident_row_blocks(K kernel, int threads, size_t lds_bytes, int64_t rows, int rows_per_block, int max_blocks, int cols = 1) {
+  int64_t nb = (rows + rows_per_block - 1) / rows_per_block;
+  if (nb > max_blocks) nb = max_blocks;
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds_bytes) == hipSuccess && per_cu >= 1) {
+    int64_t resident = (int64_t)per_cu * cu_count() / cols;
+    if (resident < 1) resident = 1;
+    if (resident < nb) nb = resident;
+  }
+  return (int)(nb < 1 ? 1 : nb);
+}
+// Finish of a row-pass backward (aux_ops.hip): column sums of the workgroups' partial rows (nparts rows of pstride floats).
+// The columns go to the segments in order, `len` each; columns past the last segment are dropped.  16 columns per block of
+// 256 threads: thread (r, cc) adds rows r, r + 16, .. of its column in order, then the 16 sums are added in index order.
+struct ColSegment {
+  float* out;
+  int64_t len;
+};
+int launch_partial_col_sums(const float* partial, int nparts, int64_t pstride, const ColSegment (&segs)[4], const char* who,
+                            hipStream_t st);
+
 // bytes of the bias tables a workgroup stages in LDS: pos_w (2N-1 floats), ts_w (nb+1 floats), N int64 timestamps,
 // their int32 offsets
 inline int bias_table_bytes(int max_seq_len, int num_buckets) {

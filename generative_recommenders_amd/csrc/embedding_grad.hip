@@ -4,18 +4,16 @@
 // (:339-407).
 //
 // 1. rows are grouped by table index with a radix sort over only the ceil(log2(table_rows)) significant key bits
-//    (rocPRIM device sort, 32-bit keys and 32-bit row numbers from a counting iterator: two digit passes for an 8 K-row
+//    (embedding_sort.cuh: rocPRIM device sort, 32-bit keys and 32-bit row numbers from a counting iterator: two digit passes for an 8 K-row
 //    table, against the eight of a full-width sort with int64 payload);
 // 2. one wave per run of 64 sorted rows: the 64 (index, row) pairs arrive with one coalesced load and are handed out
 //    lane by lane; the wave reads four rows at a time (16 bytes per lane and piece), adds them IN SORTED ORDER into fp32
 //    column sums in registers and flushes when the table index changes: a segment inside one run is written by exactly
 //    one wave with a plain store, segments cut by a run boundary add their pieces with fp32 atomics (the only
 //    non-deterministic summation order, and only for those rows).
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-
 #include "hstu_common.cuh"
 #include "capi_internal.h"
+#include "embedding_sort.cuh"
 
 namespace hstu {
 
@@ -116,27 +114,11 @@ static int seg_dispatch(const void* g, const P* perm, const int32_t* sorted_idx,
 
 static int seg_check(const char* what, const void* dout, int64_t n, int dim, int table_rows, const float* table_grad, int dtype) {
   if (!table_grad || table_rows <= 0 || dim <= 0) return set_error(HSTU_EINVAL, "%s: table_grad must be non-NULL, sizes positive", what);
-  const int es = dtype == HSTU_DTYPE_F32 ? 4 : 2;
+  const int es = dtype_bytes(dtype);
   if ((dim * es) % 16 || ((uintptr_t)dout & 15)) return set_error(HSTU_EINVAL, "%s: rows must be 16-byte multiples and 16-byte aligned", what);
   if (dim * es > kSegPieces * 64 * 16) return set_error(HSTU_EUNSUPPORTED, "%s: rows of %d bytes > %d", what, dim * es, kSegPieces * 64 * 16);
   if (n < 0 || n > 0x7fffffffLL) return set_error(HSTU_EINVAL, "%s: n out of range", what);
   return HSTU_OK;
-}
-
-static unsigned key_bits(int table_rows) {
-  unsigned bits = 1;
-  while ((1u << bits) < (unsigned)table_rows && bits < 31) ++bits;
-  return bits;
-}
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static size_t sort_temp_bytes(int64_t n, int table_rows) {
-  size_t bytes = 0;
-  rocprim::counting_iterator<int32_t> rows(0);
-  (void)rocprim::radix_sort_pairs(nullptr, bytes, (const int32_t*)nullptr, (int32_t*)nullptr, rows, (int32_t*)nullptr, (size_t)n, 0u,
-                                  key_bits(table_rows), (hipStream_t)0);
-  return bytes;
 }
 
 }  // namespace hstu
@@ -179,8 +161,7 @@ int hstu_embedding_grad(const void* dout, const int32_t* idx, int64_t n, int32_t
   int32_t* sorted_idx = (int32_t*)workspace;
   int32_t* perm = (int32_t*)((char*)workspace + part);
   void* tmp = (char*)workspace + 2 * part;
-  rocprim::counting_iterator<int32_t> rows(0);
-  e = rocprim::radix_sort_pairs(tmp, temp, idx, sorted_idx, rows, perm, (size_t)n, 0u, key_bits(table_rows), st);
+  e = sort_indices(tmp, temp, idx, sorted_idx, perm, n, table_rows, st);
   if (e != hipSuccess) return set_error(HSTU_ELAUNCH, "%s: sort failed: %s", what, hipGetErrorString(e));
   return seg_dispatch<int32_t>(dout, perm, sorted_idx, n, dim, table_grad, dtype, st, what);
 }

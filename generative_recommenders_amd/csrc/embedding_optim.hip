@@ -5,7 +5,7 @@
 // in one pass that reads the batch's gradient rows once and reads / writes only the touched table rows: no table-sized
 // gradient, no memset, O(n) workspace.
 //
-// 1. rows are grouped by id with the radix sort of embedding_grad.hip (significant key bits only, stable: the duplicates
+// 1. rows are grouped by id with the radix sort of embedding_sort.cuh (significant key bits only, stable: the duplicates
 //    of an id stay in batch order);
 // 2. chunk kernel, one wave per CHUNK of sorted positions (128 of them; 32 below 262,144 ids when dim <= 512, where 128
 //    would leave most of the chip without a wave; grid-stride).  The chunk's (id, row) pairs arrive with one
@@ -23,11 +23,9 @@
 // Every segment is finished by exactly one owner before its state is touched; there are no float atomics; the order of
 // summation is a function of the sorted positions alone (never of timing or of the grid size), so results are
 // bit-identical from run to run.
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-
 #include "hstu_common.cuh"
 #include "capi_internal.h"
+#include "embedding_sort.cuh"
 
 namespace hstu {
 
@@ -271,22 +269,6 @@ __global__ __launch_bounds__(kCombineWaves * 64) void adagrad_combine_kernel(con
   }
 }
 
-static unsigned opt_key_bits(int table_rows) {
-  unsigned bits = 1;
-  while ((1u << bits) < (unsigned)table_rows && bits < 31) ++bits;
-  return bits;
-}
-
-static size_t opt_align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static size_t opt_sort_temp_bytes(int64_t n, int table_rows) {
-  size_t bytes = 0;
-  rocprim::counting_iterator<int32_t> rows(0);
-  (void)rocprim::radix_sort_pairs(nullptr, bytes, (const int32_t*)nullptr, (int32_t*)nullptr, rows, (int32_t*)nullptr, (size_t)n, 0u,
-                                  opt_key_bits(table_rows), (hipStream_t)0);
-  return bytes;
-}
-
 struct OptLayout {
   size_t part, partials_off, temp_off, temp_bytes, total;
 };
@@ -300,11 +282,11 @@ static_assert(kChunkLarge / kChunkSmall * kSmallChunkMaxDim <= kOptMaxDim, "the 
 // size must not depend on it) | sort temporary
 static OptLayout opt_layout(int64_t n, int table_rows) {
   OptLayout l;
-  l.part = opt_align256((size_t)n * sizeof(int32_t));
+  l.part = align256((size_t)n * sizeof(int32_t));
   l.partials_off = 2 * l.part;
-  l.temp_off = l.partials_off + opt_align256(2 * (size_t)((n + kChunkLarge - 1) / kChunkLarge) * kOptMaxDim * sizeof(float));
-  l.temp_bytes = n ? opt_sort_temp_bytes(n, table_rows) : 0;
-  l.total = l.temp_off + opt_align256(l.temp_bytes);
+  l.temp_off = l.partials_off + align256(2 * (size_t)((n + kChunkLarge - 1) / kChunkLarge) * kOptMaxDim * sizeof(float));
+  l.temp_bytes = n ? sort_temp_bytes(n, table_rows) : 0;
+  l.total = l.temp_off + align256(l.temp_bytes);
   return l;
 }
 
@@ -368,9 +350,8 @@ int hstu_embedding_rowwise_adagrad(const void* dout, const int32_t* idx, int64_t
   const char* what = "hstu_embedding_rowwise_adagrad";
   if (!weight || !momentum1 || table_rows <= 0 || dim <= 0)
     return set_error(HSTU_EINVAL, "%s: weight and momentum1 must be non-NULL, sizes positive", what);
-  if (dtype != HSTU_DTYPE_BF16 && dtype != HSTU_DTYPE_F16 && dtype != HSTU_DTYPE_F32)
-    return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32", what);
-  const int es = dtype == HSTU_DTYPE_F32 ? 4 : 2;
+  if (!is_float_dtype(dtype)) return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32", what);
+  const int es = dtype_bytes(dtype);
   if (dim > kOptMaxDim)                             // before any product with dim: dim * es must not wrap
     return set_error(HSTU_EUNSUPPORTED, "%s: rows of %d columns > %d", what, dim, kOptMaxDim);
   if ((dim * es) % 16 || ((uintptr_t)dout & 15) || ((uintptr_t)weight & 15))
@@ -390,8 +371,7 @@ int hstu_embedding_rowwise_adagrad(const void* dout, const int32_t* idx, int64_t
   int32_t* perm = (int32_t*)(ws + l.part);
   float* partials = (float*)(ws + l.partials_off);
   size_t temp = l.temp_bytes;
-  rocprim::counting_iterator<int32_t> rows(0);
-  hipError_t e = rocprim::radix_sort_pairs(ws + l.temp_off, temp, idx, sorted_idx, rows, perm, (size_t)n, 0u, opt_key_bits(table_rows), st);
+  hipError_t e = sort_indices(ws + l.temp_off, temp, idx, sorted_idx, perm, n, table_rows, st);
   if (e != hipSuccess) return set_error(HSTU_ELAUNCH, "%s: sort failed: %s", what, hipGetErrorString(e));
   const OptArgs a{dout, perm, sorted_idx, n, dim, weight, momentum1, partials, lr, eps, st};
   switch (dtype) {

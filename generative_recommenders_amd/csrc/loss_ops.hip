@@ -17,7 +17,7 @@
 // every gathered table row is added to a (table_rows, dim) fp32 buffer with atomics (the summation order over rows that
 // sampled the same item is not fixed: the one non-deterministic sum of this op, as index_put(accumulate) is in the
 // reference's backward).  Rows with zero upstream gradient (masked positions: supervision weight 0) are skipped.
-#include "hstu_common.cuh"
+#include "row_pass.cuh"
 #include "capi_internal.h"
 
 namespace hstu {
@@ -25,47 +25,6 @@ namespace hstu {
 constexpr int kLossThreads = 256;
 constexpr int kLossWaves = kLossThreads / 64;
 constexpr float kMaskedLogit = -5e4f;   // sampled_softmax.py:80
-
-template <typename T> struct LossVec;
-template <> struct LossVec<float> { static constexpr int N = 4; };
-template <> struct LossVec<bf16_t> { static constexpr int N = 8; };
-template <> struct LossVec<f16_t> { static constexpr int N = 8; };
-
-// 16 bytes of a row as floats (zeros when the lane's slice is past the row)
-template <typename T>
-HSTU_DEV void load16f(float (&v)[LossVec<T>::N], const T* p, bool ok) {
-  constexpr int N = LossVec<T>::N;
-  if (!ok) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = 0.f;
-    return;
-  }
-  if constexpr (N == 8) {
-    const u32x4 x = *reinterpret_cast<const u32x4*>(p);
-    typedef T t8 __attribute__((ext_vector_type(8)));
-    const t8 t = __builtin_bit_cast(t8, x);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (float)t[i];
-  } else {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = t[i];
-  }
-}
-template <typename T>
-HSTU_DEV void store16f(const float (&v)[LossVec<T>::N], T* p) {
-  constexpr int N = LossVec<T>::N;
-  if constexpr (N == 8) {
-    typedef T t8 __attribute__((ext_vector_type(8)));
-    t8 t;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t[i] = (T)v[i];
-    *reinterpret_cast<u32x4*>(p) = __builtin_bit_cast(u32x4, t);
-  } else {
-    const f32x4 t = {v[0], v[1], v[2], v[3]};
-    *reinterpret_cast<f32x4*>(p) = t;
-  }
-}
 
 // sum over the LPE lanes of a lane group (LPE a power of two, groups aligned)
 template <int LPE>
@@ -101,7 +60,7 @@ HSTU_DEV float neg_logit(float dot, float nn, const LossArgs& a, bool masked, fl
 template <typename T, int LPE>
 __global__ __launch_bounds__(kLossThreads) void sampled_softmax_fwd_kernel(const LossArgs a, const float* g_row,
                                                                            float* row_loss, float* lse_out) {
-  constexpr int N = LossVec<T>::N;
+  constexpr int N = 16 / (int)sizeof(T);            // elements of a 16-byte piece (row_pass.cuh)
   constexpr int G = 64 / LPE;                       // negatives per wave per step
   __shared__ float sm[kLossWaves], ss[kLossWaves];
   const int64_t i = blockIdx.x;
@@ -109,8 +68,8 @@ __global__ __launch_bounds__(kLossThreads) void sampled_softmax_fwd_kernel(const
   const int sub = lane & (LPE - 1), grp = lane / LPE;
   const bool ok = sub * N < a.dim;
   float qv[N], pv[N];
-  load16f<T>(qv, (const T*)a.q + i * a.q_stride + sub * N, ok);
-  load16f<T>(pv, (const T*)a.pos + i * a.pos_stride + sub * N, ok);
+  load_piece<T, N>(qv, (const T*)a.q + i * a.q_stride + sub * N, ok);
+  load_piece<T, N>(pv, (const T*)a.pos + i * a.pos_stride + sub * N, ok);
   const int64_t pid = a.pos_ids[i];
   float dp = 0.f, pp = 0.f;
 #pragma unroll
@@ -129,7 +88,7 @@ __global__ __launch_bounds__(kLossThreads) void sampled_softmax_fwd_kernel(const
     r = r < 0 ? 0 : (r >= a.table_rows ? a.table_rows - 1 : r);     // memory safety; a bad index is the caller's bug
     const bool masked = live && ids[k] == pid;
     float nv[N];
-    load16f<T>(nv, (const T*)a.table + r * a.table_stride + sub * N, ok && live);
+    load_piece<T, N>(nv, (const T*)a.table + r * a.table_stride + sub * N, ok && live);
     float d = 0.f, nn = 0.f;
 #pragma unroll
     for (int f = 0; f < N; ++f) { d += qv[f] * nv[f]; nn += nv[f] * nv[f]; }
@@ -163,7 +122,7 @@ template <typename T, int LPE>
 __global__ __launch_bounds__(kLossThreads) void sampled_softmax_bwd_kernel(const LossArgs a, const float* lse_in,
                                                                            const float* g_row, T* dq, int64_t dq_stride,
                                                                            T* dpos, int64_t dpos_stride, float* dtable) {
-  constexpr int N = LossVec<T>::N;
+  constexpr int N = 16 / (int)sizeof(T);            // elements of a 16-byte piece (row_pass.cuh)
   constexpr int G = 64 / LPE;
   __shared__ float red[kLossWaves][LPE * N];
   __shared__ __attribute__((aligned(16))) float tr[kLossWaves][64 * N];   // per-wave transpose tile
@@ -177,14 +136,14 @@ __global__ __launch_bounds__(kLossThreads) void sampled_softmax_bwd_kernel(const
   for (int f = 0; f < N; ++f) zero[f] = 0.f;
   if (g == 0.f) {   // masked position: exact zeros, nothing gathered
     if (wave == 0 && grp == 0 && ok) {
-      store16f<T>(zero, dq + i * dq_stride + sub * N);
-      store16f<T>(zero, dpos + i * dpos_stride + sub * N);
+      store_piece<T, N, false>(zero, dq + i * dq_stride + sub * N);
+      store_piece<T, N, false>(zero, dpos + i * dpos_stride + sub * N);
     }
     return;
   }
   float qv[N], pv[N];
-  load16f<T>(qv, (const T*)a.q + i * a.q_stride + sub * N, ok);
-  load16f<T>(pv, (const T*)a.pos + i * a.pos_stride + sub * N, ok);
+  load_piece<T, N>(qv, (const T*)a.q + i * a.q_stride + sub * N, ok);
+  load_piece<T, N>(pv, (const T*)a.pos + i * a.pos_stride + sub * N, ok);
   const int64_t pid = a.pos_ids[i];
   const float lse = lse_in[i];
   float dp = 0.f, pp = 0.f;
@@ -209,7 +168,7 @@ __global__ __launch_bounds__(kLossThreads) void sampled_softmax_bwd_kernel(const
     r = r < 0 ? 0 : (r >= a.table_rows ? a.table_rows - 1 : r);
     const bool masked = live && ids[k] == pid;
     float nv[N];
-    load16f<T>(nv, (const T*)a.table + r * a.table_stride + sub * N, ok && live);
+    load_piece<T, N>(nv, (const T*)a.table + r * a.table_stride + sub * N, ok && live);
     float d = 0.f, nn = 0.f;
 #pragma unroll
     for (int f = 0; f < N; ++f) { d += qv[f] * nv[f]; nn += nv[f] * nv[f]; }
@@ -271,8 +230,8 @@ __global__ __launch_bounds__(kLossThreads) void sampled_softmax_bwd_kernel(const
       o[f] = acc + c0 * inv_pc * pv[f];
       dpv[f] = c0 * inv_pc * qv[f] - pproj * pv[f];
     }
-    store16f<T>(o, dq + i * dq_stride + sub * N);
-    store16f<T>(dpv, dpos + i * dpos_stride + sub * N);
+    store_piece<T, N, false>(o, dq + i * dq_stride + sub * N);
+    store_piece<T, N, false>(dpv, dpos + i * dpos_stride + sub * N);
   }
 }
 
@@ -293,7 +252,7 @@ static int loss_launch_lpe(const LossArgs& a, bool bwd, const float* lse_in, con
 template <typename T>
 static int loss_launch(const LossArgs& a, bool bwd, const float* lse_in, const float* g_row, float* row_loss, float* lse_out,
                        void* dq, int64_t dq_stride, void* dpos, int64_t dpos_stride, float* dtable, hipStream_t st) {
-  const int units = a.dim / LossVec<T>::N;   // 16-byte units per embedding
+  const int units = a.dim / (16 / (int)sizeof(T));   // 16-byte units per embedding
 #define LPE_CASE(L) \
   if (units <= L) return loss_launch_lpe<T, L>(a, bwd, lse_in, g_row, row_loss, lse_out, dq, dq_stride, dpos, dpos_stride, dtable, st);
   LPE_CASE(1) LPE_CASE(2) LPE_CASE(4) LPE_CASE(8) LPE_CASE(16) LPE_CASE(32) LPE_CASE(64)

@@ -11,7 +11,9 @@
 // which reads x a second time) so that no instance needs more than 64 accumulators per array.  The T values of a row live in
 // lanes 0 .. T-1.  Every sum over rows is a per-lane sum in row order, a fixed-order sum over the workgroup's waves through LDS,
 // one partial per workgroup in the workspace and a fixed-order finish kernel: no float atomics, bit-identical run to run.
-#include "hstu_common.cuh"
+// Pieces, wave sums and the sum over the waves are row_pass.cuh's; the grid rule and the backward's finish kernel
+// (launch_partial_col_sums, aux_ops.hip) are capi_internal.h's.
+#include "row_pass.cuh"
 #include "capi_internal.h"
 
 namespace hstu {
@@ -44,48 +46,6 @@ struct MtBwdArgs {
   float* partial;
   int64_t rows; int dim; int tasks; int nbin; float loss_scale;
 };
-
-template <typename T, int VEC>
-HSTU_DEV void load_piece(float (&v)[VEC], const T* p, bool ok) {
-  if (!ok) {
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) v[i] = 0.f;
-    return;
-  }
-  if constexpr (VEC == 1) {
-    v[0] = (float)p[0];
-  } else {
-    static_assert(VEC * sizeof(T) == 16, "a 16-byte piece");
-    typedef T tv __attribute__((ext_vector_type(VEC)));
-    const tv t = __builtin_bit_cast(tv, *reinterpret_cast<const u32x4*>(p));
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) v[i] = (float)t[i];
-  }
-}
-
-template <typename T, int VEC>
-HSTU_DEV void store_piece(const float (&v)[VEC], T* p) {
-  if constexpr (VEC == 1) {
-    p[0] = (T)v[0];
-  } else {
-    typedef T tv __attribute__((ext_vector_type(VEC)));
-    tv t;
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) t[i] = (T)v[i];
-    __builtin_nontemporal_store(__builtin_bit_cast(u32x4, t), reinterpret_cast<u32x4*>(p));
-  }
-}
-
-HSTU_DEV float mt_wave_sum(float x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
-}
-
-// lane t's value in every lane (t a constant of the unrolled task loop: one v_readlane, no LDS crossbar)
-HSTU_DEV float lane_value(float v, int t) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), t));
-}
 
 // the T values of a row are computed once, in lanes 0 .. T-1: IEEE exp / log1p / divide there (T <= 8 per row), the hardware
 // exp2 / rcp only for the row's dim sigmoids of the gate
@@ -141,7 +101,7 @@ __global__ __launch_bounds__(kMtThreads) void multitask_head_fwd_kernel(const Mt
 #pragma unroll
       for (int i = 0; i < VEC; ++i) s += xv[k][i];
     }
-    const float mean = mt_wave_sum(s) / dim;
+    const float mean = wave_sum(s) / dim;
     float q = 0.f;
 #pragma unroll
     for (int k = 0; k < MC; ++k) {
@@ -151,7 +111,7 @@ __global__ __launch_bounds__(kMtThreads) void multitask_head_fwd_kernel(const Mt
         for (int i = 0; i < VEC; ++i) { const float d = xv[k][i] - mean; q += d * d; }
       }
     }
-    const float rstd = 1.0f / sqrtf(mt_wave_sum(q) / dim + a.eps);
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / dim + a.eps);
     float part[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) part[t] = 0.f;
@@ -187,7 +147,7 @@ __global__ __launch_bounds__(kMtThreads) void multitask_head_fwd_kernel(const Mt
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       if (t < tasks) {
-        const float p = mt_wave_sum(part[t]);
+        const float p = wave_sum(part[t]);
         if (lane == t) z = p;
       }
     }
@@ -301,22 +261,6 @@ HSTU_DEV void piece_backward(const float (&xv)[VEC], const float (&gv)[VEC], con
   }
 }
 
-// sum over the workgroup's waves of one per-lane array of column partials -> out[c0 .. c0 + 64 VEC) (columns < dim)
-template <int VEC>
-HSTU_DEV void block_sum_cols(const float (&acc)[VEC], float* lds, float* out, int c0, int dim) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) lds[wave * 64 * VEC + lane * VEC + i] = acc[i];
-  __syncthreads();
-  for (int c = threadIdx.x; c < 64 * VEC; c += kMtThreads) {
-    float s = 0.f;
-#pragma unroll
-    for (int w2 = 0; w2 < kMtWaves; ++w2) s += lds[w2 * 64 * VEC + c];
-    if (c0 + c < dim) out[c0 + c] = s;
-  }
-  __syncthreads();
-}
-
 // Columns [blockIdx.y 64 VEC, +64 VEC) of every row: per-lane partials of dW, dg, db (and dc in column group 0) in
 // registers.  DX (rows of one column group, gridDim.y == 1): the row sums of the norm's backward are complete inside the
 // wave, so dx is written here too and x is read exactly once.
@@ -366,12 +310,12 @@ __global__ __launch_bounds__(kMtThreads, 2) void multitask_head_bwd_kernel(const
       }
     }
     if constexpr (DX) {
-      const float c1 = mt_wave_sum(s1) / dim, c2 = mt_wave_sum(s2) / dim;
+      const float c1 = wave_sum(s1) / dim, c2 = wave_sum(s2) / dim;
       if (ok) {
         float o[VEC];
 #pragma unroll
         for (int i = 0; i < VEC; ++i) o[i] = rstd * (dz[i] - c2 - xhat[i] * c1) + direct[i];
-        store_piece<T, VEC>(o, (T*)a.dx + row * a.dx_rs + c);
+        store_piece<T, VEC, true>(o, (T*)a.dx + row * a.dx_rs + c);
       }
     }
   }
@@ -379,9 +323,9 @@ __global__ __launch_bounds__(kMtThreads, 2) void multitask_head_bwd_kernel(const
   float* prow = a.partial + (int64_t)blockIdx.x * pstride;
 #pragma unroll
   for (int t = 0; t < NT; ++t)
-    if (t < tasks) block_sum_cols<VEC>(dw[t], lds, prow + (int64_t)t * dim, c0, dim);
-  block_sum_cols<VEC>(dg, lds, prow + (int64_t)tasks * dim, c0, dim);
-  block_sum_cols<VEC>(db, lds, prow + (int64_t)(tasks + 1) * dim, c0, dim);
+    if (t < tasks) block_sum_cols<VEC, kMtWaves>(dw[t], lds, prow + (int64_t)t * dim, c0, dim);
+  block_sum_cols<VEC, kMtWaves>(dg, lds, prow + (int64_t)tasks * dim, c0, dim);
+  block_sum_cols<VEC, kMtWaves>(db, lds, prow + (int64_t)(tasks + 1) * dim, c0, dim);
   if (blockIdx.y == 0) {
     if (lane < kMtMaxTasks) lds[wave * kMtMaxTasks + lane] = dcacc;
     __syncthreads();
@@ -437,58 +381,21 @@ __global__ __launch_bounds__(kMtThreads) void multitask_head_bwd_dx_kernel(const
             float o[VEC];
 #pragma unroll
             for (int i = 0; i < VEC; ++i) o[i] = rstd * (dz[i] * gv[i] - c2 - xhat[i] * c1) + direct[i];
-            store_piece<T, VEC>(o, (T*)a.dx + row * a.dx_rs + c);
+            store_piece<T, VEC, true>(o, (T*)a.dx + row * a.dx_rs + c);
           }
         }
       }
-      if (sweep == 0) { c1 = mt_wave_sum(s1) / dim; c2 = mt_wave_sum(s2) / dim; }
+      if (sweep == 0) { c1 = wave_sum(s1) / dim; c2 = wave_sum(s2) / dim; }
     }
   }
 }
 
-// Column sums of the workgroups' backward partials (nparts rows of `pstride` floats): 16 columns per block, thread
-// (r, cc) adds rows r, r + 16, .. of column cc in order (64-byte segments), then the 16 sums are added in order.
-__global__ __launch_bounds__(256) void multitask_head_bwd_finish_kernel(const float* partial, int nparts, int64_t pstride, int tasks,
-                                                                        int dim, float* dw, float* dc, float* dg, float* db) {
-  __shared__ float red[16][17];
-  const int cc = threadIdx.x & 15, r = threadIdx.x >> 4;
-  const int64_t col = (int64_t)blockIdx.x * 16 + cc;
-  float s = 0.f;
-  if (col < pstride)
-    for (int i = r; i < nparts; i += 16) s += partial[(int64_t)i * pstride + col];
-  red[r][cc] = s;
-  __syncthreads();
-  if (r == 0 && col < pstride) {
-    float tot = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) tot += red[k][cc];
-    const int64_t wcols = (int64_t)tasks * dim;
-    if (col < wcols) dw[col] = tot;
-    else if (col < wcols + dim) dg[col - wcols] = tot;
-    else if (col < wcols + 2 * dim) db[col - wcols - dim] = tot;
-    else if (col - wcols - 2 * dim < tasks) dc[col - wcols - 2 * dim] = tot;
-  }
-}
-
 // ------------------------------------------------------------------ host side
-static int mt_row_blocks(int64_t rows) {
-  const int64_t b = (rows + kMtWaves - 1) / kMtWaves;
-  return (int)(b > kMtMaxBlocks ? kMtMaxBlocks : (b < 1 ? 1 : b));
-}
-
-// the workgroups that are resident at once (every wave then walks the same number of rows), at most kMtMaxBlocks
+// the kernel's LDS reserved, and its resident grid (at most kMtMaxBlocks)
 template <typename K>
 static int mt_launch_blocks(K kernel, size_t lds, int64_t rows, const char* who, int* nb) {
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return set_error(HSTU_ELAUNCH, "%s: cannot reserve %zu bytes of LDS: %s", who, lds, hipGetErrorString(e));
-  }
-  int per_cu = 0;
-  *nb = mt_row_blocks(rows);
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kMtThreads, lds) == hipSuccess && per_cu >= 1) {
-    const int64_t resident = (int64_t)per_cu * cu_count();
-    if (resident < *nb) *nb = (int)resident;
-  }
+  if (int e = reserve_lds((const void*)kernel, (int)lds, who)) return e;
+  *nb = resident_row_blocks(kernel, kMtThreads, lds, rows, kMtWaves, kMtMaxBlocks);
   return HSTU_OK;
 }
 
@@ -531,9 +438,7 @@ static int bwd_go(MtBwdArgs a, float* dw, float* dc, float* dg, float* db, hipSt
   }
   if (int e = check_launch(who)) return e;
   const int64_t pstride = (int64_t)(a.tasks + 2) * a.dim + kMtMaxTasks;
-  hipLaunchKernelGGL(multitask_head_bwd_finish_kernel, dim3((unsigned)((pstride + 15) / 16)), dim3(256), 0, st, a.partial, nb, pstride,
-                     a.tasks, a.dim, dw, dc, dg, db);
-  return check_launch(who);
+  return launch_partial_col_sums(a.partial, nb, pstride, {{dw, (int64_t)a.tasks * a.dim}, {dg, a.dim}, {db, a.dim}, {dc, a.tasks}}, who, st);
 }
 
 // rows of 16-byte pieces (vec) or of single elements; one column group or the widest row; one task or up to eight

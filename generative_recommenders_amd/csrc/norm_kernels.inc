@@ -21,60 +21,18 @@ template <typename T, int VEC> struct RowVec {
   float v[VEC];
 };
 
-template <typename T, int VEC>
-HSTU_DEV void load_vec(RowVec<T, VEC>& r, const T* p, bool ok) {
-  if (!ok) {
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) r.v[i] = 0.f;
-    return;
-  }
-  if constexpr (VEC == 1) {
-    r.v[0] = (float)p[0];
-  } else if constexpr (sizeof(T) == 2) {  // VEC == 8
-    u32x4 x = *reinterpret_cast<const u32x4*>(p);   // (the non-temporal hint on these loads: mixed, norm_mul bwd +6 %; profiles/r04_norm_nt.txt)
-    typedef T t8 __attribute__((ext_vector_type(8)));
-    t8 t = __builtin_bit_cast(t8, x);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r.v[i] = (float)t[i];
-  } else {  // fp32, VEC == 4
-    f32x4 t = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r.v[i] = t[i];
-  }
-}
+// The pieces are row_pass.cuh's.  A row's pieces are loaded with load_piece<T, VEC>(r.v, ..) itself: a load_vec wrapper
+// around it -- one more level of inlining around its early return -- changes the register allocation of 71 of this
+// file's 254 kernels.  (The non-temporal hint on the loads: mixed, norm_mul bwd +6 %; profiles/r04_norm_nt.txt)
 
+// (stores: non-temporal for the 16-bit dtypes: layer norm fwd 81 -> 68 us, SiLU fwd 81 -> 62 us, the others -1..-3 %, layer step
+// unchanged; profiles/r04_norm_nt.txt.  fp32 pieces: plain stores)
 template <typename T, int VEC>
-HSTU_DEV void store_vec(const RowVec<T, VEC>& r, T* p) {
-  if constexpr (VEC == 1) {
-    p[0] = (T)r.v[0];
-  } else if constexpr (sizeof(T) == 2) {
-    typedef T t8 __attribute__((ext_vector_type(8)));
-    t8 t;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t[i] = (T)r.v[i];
-    // (non-temporal: layer norm fwd 81 -> 68 us, SiLU fwd 81 -> 62 us, the others -1..-3 %, layer step unchanged; profiles/r04_norm_nt.txt)
-    __builtin_nontemporal_store(__builtin_bit_cast(u32x4, t), reinterpret_cast<u32x4*>(p));
-  } else {
-    f32x4 t = {r.v[0], r.v[1], r.v[2], r.v[3]};
-    *reinterpret_cast<f32x4*>(p) = t;
-  }
-}
+HSTU_DEV void store_vec(const RowVec<T, VEC>& r, T* p) { store_piece<T, VEC, sizeof(T) == 2>(r.v, p); }
 
 // 16-byte piece as loaded (prefetch of the next row: 4 registers instead of the 8 of its fp32 expansion) and its expansion
 template <typename T> HSTU_DEV u32x4 load_raw16(const T* p) { return *reinterpret_cast<const u32x4*>(p); }
-template <typename T, int VEC> HSTU_DEV void expand_raw16(RowVec<T, VEC>& r, u32x4 x) {
-  static_assert(VEC * sizeof(T) == 16, "a 16-byte piece");
-  typedef T tv __attribute__((ext_vector_type(VEC)));
-  tv t = __builtin_bit_cast(tv, x);
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) r.v[i] = (float)t[i];
-}
-
-HSTU_DEV float wave_sum(float x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
-}
+template <typename T, int VEC> HSTU_DEV void expand_raw16(RowVec<T, VEC>& r, u32x4 x) { expand_piece<T, VEC>(r.v, x); }
 
 // ------------------------------------------------------------------ fused dropout of the output stage
 // Replaces the Philox dropout inside _ln_mul_dropout_fwd / _group_norm_mul_dropout_fwd (triton_hstu_linear.py:101-120,
@@ -180,8 +138,8 @@ __global__ __launch_bounds__(kNormThreads) void layer_norm_fwd_kernel(const T* x
 #pragma unroll
   for (int k = 0; k < MC; ++k) {
     const int c = (k * 64 + lane) * VEC;
-    load_vec<T, VEC>(wv[k], w + c, k < nch && c < dim);
-    load_vec<T, VEC>(bv[k], b + c, k < nch && c < dim);
+    load_piece<T, VEC>(wv[k].v, w + c, k < nch && c < dim);
+    load_piece<T, VEC>(bv[k].v, b + c, k < nch && c < dim);
   }
   for (int64_t row = (int64_t)blockIdx.x * kNormWaves + wave; row < rows; row += (int64_t)gridDim.x * kNormWaves) {
     RowVec<T, VEC> xv[MC];
@@ -189,7 +147,7 @@ __global__ __launch_bounds__(kNormThreads) void layer_norm_fwd_kernel(const T* x
 #pragma unroll
     for (int k = 0; k < MC; ++k) {
       const int c = (k * 64 + lane) * VEC;
-      load_vec<T, VEC>(xv[k], x + row * dim + c, k < nch && c < dim);
+      load_piece<T, VEC>(xv[k].v, x + row * dim + c, k < nch && c < dim);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) s += xv[k].v[i];
     }
@@ -261,8 +219,8 @@ __global__ __launch_bounds__(kNormThreads) void layer_norm_bwd_kernel(const T* d
 #pragma unroll
   for (int k = 0; k < MC; ++k) {
     const int c = (k * 64 + lane) * VEC;
-    load_vec<T, VEC>(wv[k], w + c, k < nch && c < dim);
-    if constexpr (SWISH) load_vec<T, VEC>(bv[k], b + c, k < nch && c < dim);
+    load_piece<T, VEC>(wv[k].v, w + c, k < nch && c < dim);
+    if constexpr (SWISH) load_piece<T, VEC>(bv[k].v, b + c, k < nch && c < dim);
 #pragma unroll
     for (int i = 0; i < VEC; ++i) { dw[k][i] = 0.f; db[k][i] = 0.f; }
   }
@@ -276,8 +234,8 @@ __global__ __launch_bounds__(kNormThreads) void layer_norm_bwd_kernel(const T* d
       const int c = (k * 64 + lane) * VEC;
       const bool ok = k < nch && c < dim;
       RowVec<T, VEC> dyv;
-      load_vec<T, VEC>(xh[k], x + row * dim + c, ok);
-      load_vec<T, VEC>(dyv, dy + row * dim + c, ok);
+      load_piece<T, VEC>(xh[k].v, x + row * dim + c, ok);
+      load_piece<T, VEC>(dyv.v, dy + row * dim + c, ok);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
         const float xhat = ok ? (xh[k].v[i] - mean) * rstd : 0.f;
@@ -309,7 +267,7 @@ __global__ __launch_bounds__(kNormThreads) void layer_norm_bwd_kernel(const T* d
         if (dres) {   // kernel-uniform: + the gradient that reaches x around the norm (the layer's residual), as the
                       // framework's add of two T tensors would form it
           RowVec<T, VEC> rv;
-          load_vec<T, VEC>(rv, dres + row * dim + c, true);
+          load_piece<T, VEC>(rv.v, dres + row * dim + c, true);
 #pragma unroll
           for (int i = 0; i < VEC; ++i) o.v[i] = __fadd_rn((float)(T)o.v[i], rv.v[i]);   // (no contraction with the product above: fp32 rows)
         }
@@ -361,8 +319,8 @@ __global__ __launch_bounds__(kNormThreads) void norm_mul_fwd_kernel(const T* att
     for (int k = 0; k < max_chunks<VEC>(); ++k) {
       const int c = (k * 64 + lane) * VEC;
       const bool ok = k < nch && c < dim;
-      load_vec<T, VEC>(xv[k], attn + row * dim + c, ok);
-      load_vec<T, VEC>(uv[k], u + row * us.u_stride + c, ok);
+      load_piece<T, VEC>(xv[k].v, attn + row * dim + c, ok);
+      load_piece<T, VEC>(uv[k].v, u + row * us.u_stride + c, ok);
       if constexpr (SILU) silu_rounded<T, VEC>(uv[k]);
     }
     const int ngroups = GN ? heads : 1;
@@ -394,7 +352,7 @@ __global__ __launch_bounds__(kNormThreads) void norm_mul_fwd_kernel(const T* att
         const int c = (k * 64 + lane) * VEC;
         if (k < nch && c >= lo && c < hi) {
           RowVec<T, VEC> wv, bv, o;
-          if (!GN) { load_vec<T, VEC>(wv, w + c, true); load_vec<T, VEC>(bv, b + c, true); }
+          if (!GN) { load_piece<T, VEC>(wv.v, w + c, true); load_piece<T, VEC>(bv.v, b + c, true); }
 #pragma unroll
           for (int i = 0; i < VEC; ++i) {
             const float n = (xv[k].v[i] - mean) * rstd * (GN ? gw : wv.v[i]) + (GN ? gb : bv.v[i]);
@@ -457,10 +415,10 @@ __global__ __launch_bounds__(kNormThreads) void norm_mul_bwd_kernel(const T* dy,
     for (int k = 0; k < max_chunks<VEC>(); ++k) {
       const int c = (k * 64 + lane) * VEC;
       const bool ok = k < nch && c < dim;
-      load_vec<T, VEC>(xv[k], attn + row * dim + c, ok);
-      load_vec<T, VEC>(uv[k], u + row * us.u_stride + c, ok);
+      load_piece<T, VEC>(xv[k].v, attn + row * dim + c, ok);
+      load_piece<T, VEC>(uv[k].v, u + row * us.u_stride + c, ok);
       if constexpr (SILU) { up[k] = uv[k]; silu_rounded<T, VEC>(uv[k]); }
-      load_vec<T, VEC>(gy[k], dyrow + (concat ? 2 * dim : 0) + c, ok);
+      load_piece<T, VEC>(gy[k].v, dyrow + (concat ? 2 * dim : 0) + c, ok);
       if (dc.thr && ok) drop_apply<T, VEC>(gy[k], row * istride + (concat ? 2 * dim : 0) + c, dc);   // d y3 -> d y: same mask, same scale
     }
 #pragma unroll
@@ -477,7 +435,7 @@ __global__ __launch_bounds__(kNormThreads) void norm_mul_bwd_kernel(const T* dy,
           const int c = (k * 64 + lane) * VEC;
           const bool in = k < nch && c >= lo && c < hi;
           RowVec<T, VEC> wv, bv;
-          if (!GN) { load_vec<T, VEC>(wv, w + c, in); load_vec<T, VEC>(bv, b + c, in); }
+          if (!GN) { load_piece<T, VEC>(wv.v, w + c, in); load_piece<T, VEC>(bv.v, b + c, in); }
 #pragma unroll
           for (int i = 0; i < VEC; ++i) {
             const float xhat = in ? (xv[k].v[i] - mean) * rstd : 0.f;
@@ -501,8 +459,8 @@ __global__ __launch_bounds__(kNormThreads) void norm_mul_bwd_kernel(const T* dy,
           if (k < nch && c >= lo && c < hi) {
             RowVec<T, VEC> o, o2, e1, e2;
             if (concat) {
-              load_vec<T, VEC>(e1, dyrow + c, true);          // d u   from the concat slot
-              load_vec<T, VEC>(e2, dyrow + dim + c, true);    // d attn from the concat slot
+              load_piece<T, VEC>(e1.v, dyrow + c, true);          // d u   from the concat slot
+              load_piece<T, VEC>(e2.v, dyrow + dim + c, true);    // d attn from the concat slot
               if (dc.thr) {
                 drop_apply<T, VEC>(e1, row * istride + c, dc);
                 drop_apply<T, VEC>(e2, row * istride + dim + c, dc);
@@ -590,8 +548,8 @@ __global__ __launch_bounds__(kNormThreads) void norm_mul_fwd_gn_kernel(const T* 
       for (int k = 0; k < MC; ++k) {
         const int c = (k * 64 + lane) * VEC;
         const bool ok = k < nch && c < dim;
-        load_vec<T, VEC>(xv[k], attn + row * dim + c, ok);
-        load_vec<T, VEC>(uv[k], u + row * us.u_stride + c, ok);
+        load_piece<T, VEC>(xv[k].v, attn + row * dim + c, ok);
+        load_piece<T, VEC>(uv[k].v, u + row * us.u_stride + c, ok);
       }
     }
     if constexpr (SILU) {
@@ -708,18 +666,18 @@ __global__ __launch_bounds__(kNormThreads, (MC == 1 ? 5 : 1)) void norm_mul_bwd_
       gr = load_raw16(dy + nrow * istride + gy_off + c0);
       mr = mean_in[nrow * heads + head[0]];
       rr = rstd_in[nrow * heads + head[0]];
-      load_vec<T, VEC>(e1[0], dyrow + c0, ok && concat);           // d u    from the concat slot
-      load_vec<T, VEC>(e2[0], dyrow + dim + c0, ok && concat);     // d attn from the concat slot
+      load_piece<T, VEC>(e1[0].v, dyrow + c0, ok && concat);           // d u    from the concat slot
+      load_piece<T, VEC>(e2[0].v, dyrow + dim + c0, ok && concat);     // d attn from the concat slot
     } else {
 #pragma unroll
       for (int k = 0; k < MC; ++k) {   // every load of the row is issued before anything is used
         const int c = (k * 64 + lane) * VEC;
         const bool ok = k < nch && c < dim;
-        load_vec<T, VEC>(xv[k], attn + row * dim + c, ok);
-        load_vec<T, VEC>(uv[k], u + row * us.u_stride + c, ok);
-        load_vec<T, VEC>(gy[k], dyrow + (concat ? 2 * dim : 0) + c, ok);
-        load_vec<T, VEC>(e1[k], dyrow + c, ok && concat);           // d u    from the concat slot
-        load_vec<T, VEC>(e2[k], dyrow + dim + c, ok && concat);     // d attn from the concat slot
+        load_piece<T, VEC>(xv[k].v, attn + row * dim + c, ok);
+        load_piece<T, VEC>(uv[k].v, u + row * us.u_stride + c, ok);
+        load_piece<T, VEC>(gy[k].v, dyrow + (concat ? 2 * dim : 0) + c, ok);
+        load_piece<T, VEC>(e1[k].v, dyrow + c, ok && concat);           // d u    from the concat slot
+        load_piece<T, VEC>(e2[k].v, dyrow + dim + c, ok && concat);     // d attn from the concat slot
         mean[k] = ok ? mean_in[row * heads + head[k]] : 0.f;
         rstd[k] = ok ? rstd_in[row * heads + head[k]] : 0.f;
       }
@@ -813,34 +771,16 @@ __global__ void silu_kernel(const T* dout, const T* in, T* out, int64_t rows, in
 }
 
 // ------------------------------------------------------------------ host-side dispatch
-static int norm_blocks(int64_t rows) {
-  int64_t b = (rows + kNormWaves - 1) / kNormWaves;
-  if (b > kMaxNormBlocks) b = kMaxNormBlocks;
-  return b < 1 ? 1 : (int)b;
-}
-// Grid of a row kernel with a grid-stride loop: exactly the workgroups that are resident at once (occupancy x CUs), so
-// that every wave walks the same number of rows and none starts late.  (kMaxNormBlocks = 2048 workgroups on 256 CUs ask
-// for 8 per CU; a kernel of 69 registers holds 7 -- the 256 left over ran as a second round at one seventh of the
-// occupancy.)
-template <typename K>
-static int norm_blocks_resident(K kernel, size_t lds, int64_t rows) {
-  int per_cu = 0, dev = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kNormThreads, lds) != hipSuccess || per_cu < 1) return norm_blocks(rows);
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-    return norm_blocks(rows);
-  const int64_t resident = (int64_t)per_cu * cus;
-  const int nb = norm_blocks(rows);
-  return (int)(resident < nb ? resident : nb);
-}
-
 // The launchers below take the class of the call (piece width, chunk class, group-norm path) from norm_ops.hip, which
 // decided it -- and this instance, and whether the row is accepted at all -- with norm_dispatch.h; nothing is derived here.
 using norm_dispatch::RowClass;
 
 // Launch of a row kernel on the grid that is resident at once (nb: out, the bwd launchers hand it to the reduction).
+// (kMaxNormBlocks = 2048 workgroups on 256 CUs ask for 8 per CU; a kernel of 69 registers holds 7 -- the 256 left over ran
+// as a second round at one seventh of the occupancy.)
 #define ROW_LAUNCH(NB, LDS, K, ...)                                                        \
   do {                                                                                     \
-    NB = norm_blocks_resident(K, LDS, rows);                                               \
+    NB = resident_row_blocks(K, kNormThreads, LDS, rows, kNormWaves, kMaxNormBlocks);      \
     hipLaunchKernelGGL(K, dim3(NB), dim3(kNormThreads), LDS, st, __VA_ARGS__);             \
   } while (0)
 
@@ -944,8 +884,8 @@ __global__ __launch_bounds__(256) void silu_vec_kernel(const T* dout, const T* i
     const int64_t r = i / ppr;
     const int c = (int)(i - r * ppr) * VEC;
     RowVec<T, VEC> x, g, o;
-    load_vec<T, VEC>(x, in + r * s_in + c, true);
-    if (BWD) load_vec<T, VEC>(g, dout + r * s_dout + c, true);
+    load_piece<T, VEC>(x.v, in + r * s_in + c, true);
+    if (BWD) load_piece<T, VEC>(g.v, dout + r * s_dout + c, true);
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
       o.v[k] = BWD ? silu_grad_val(g.v[k], x.v[k]) : silu_val(x.v[k]);
@@ -988,8 +928,8 @@ __global__ __launch_bounds__(kNormThreads) void l2_norm_kernel(const T* x, const
     for (int k = 0; k < max_chunks<VEC>(); ++k) {
       const int c = (k * 64 + lane) * VEC;
       const bool ok = k < nch && c < dim;
-      load_vec<T, VEC>(xv[k], x + row * dim + c, ok);
-      if (BWD) load_vec<T, VEC>(gv[k], g + row * dim + c, ok);
+      load_piece<T, VEC>(xv[k].v, x + row * dim + c, ok);
+      if (BWD) load_piece<T, VEC>(gv[k].v, g + row * dim + c, ok);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) { ss += xv[k].v[i] * xv[k].v[i]; if (BWD) dot += xv[k].v[i] * gv[k].v[i]; }
     }

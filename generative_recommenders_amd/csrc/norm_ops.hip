@@ -9,7 +9,9 @@
 //   ops/pytorch/pt_layer_norm.py:24-38, ops/pytorch/pt_hstu_linear.py:23-65;
 // kernels replaced: ops/triton/triton_layer_norm.py:77-309,
 // ops/triton/triton_hstu_linear.py:48-337 (LN * u), :570-1036 (GroupNorm * u).
-#include "hstu_common.cuh"
+// The pieces and the wave sum are row_pass.cuh's, the grid rule capi_internal.h's (resident_row_blocks): shared with the
+// later row-pass ops (multitask_ops.hip, time_ln_ops.hip, loss_ops.hip).
+#include "row_pass.cuh"
 #include "drop_hash.cuh"
 #include "capi_internal.h"
 #include "norm_dispatch.h"
@@ -32,7 +34,6 @@ namespace nw4 {
 using nw1::kMaxNormBlocks;
 using nw1::silu_launch;
 using norm_dispatch::RowClass;
-static int elem_bytes_of(int dtype) { return dtype == HSTU_DTYPE_F32 ? 4 : 2; }
 static int accept_row(const RowClass& k, int dim, const char* who) {
   if (dim <= 0) return set_error(HSTU_EINVAL, "%s: dim must be positive", who);
   if (norm_dispatch::refused(k, dim))
@@ -66,7 +67,7 @@ int hstu_layer_norm_fwd(const void* x, const void* weight, const void* bias, voi
   if (rows == 0) return HSTU_OK;
   if (!x || !weight || !bias || !y) return set_error(HSTU_EINVAL, "layer_norm_fwd: NULL tensor");
   hipStream_t st = (hipStream_t)stream;
-  const RowClass k = norm_dispatch::ln_fwd_class(dim, elem_bytes_of(dtype), x, weight, bias, y);
+  const RowClass k = norm_dispatch::ln_fwd_class(dim, dtype_bytes(dtype), x, weight, bias, y);
   if (int e = accept_row(k, dim, "layer_norm_fwd")) return e;
   DISPATCH_DTYPE(dtype, NW(k, ln_fwd<bf16_t>(k, x, weight, bias, y, mean, rstd, rows, dim, eps, st)),
                  NW(k, ln_fwd<f16_t>(k, x, weight, bias, y, mean, rstd, rows, dim, eps, st)),
@@ -91,7 +92,7 @@ int hstu_layer_norm_bwd_residual(const void* dy, const void* x, const void* weig
     return HSTU_OK;
   }
   if (!dy || !x || !weight || !mean || !rstd || !dx || !partial_ws) return set_error(HSTU_EINVAL, "layer_norm_bwd: NULL tensor");
-  const RowClass k = norm_dispatch::ln_bwd_class(dim, elem_bytes_of(dtype), dy, x, weight, nullptr, dres, dx);
+  const RowClass k = norm_dispatch::ln_bwd_class(dim, dtype_bytes(dtype), dy, x, weight, nullptr, dres, dx);
   if (int e = accept_row(k, dim, "layer_norm_bwd")) return e;
   DISPATCH_DTYPE(dtype, NW(k, ln_bwd<bf16_t>(k, dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, dres, st)),
                  NW(k, ln_bwd<f16_t>(k, dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, dres, st)),
@@ -104,7 +105,7 @@ int hstu_swish_layer_norm_fwd(const void* x, const void* weight, const void* bia
   if (rows == 0) return HSTU_OK;
   if (!x || !weight || !bias || !y) return set_error(HSTU_EINVAL, "swish_layer_norm_fwd: NULL tensor");
   hipStream_t st = (hipStream_t)stream;
-  const RowClass k = norm_dispatch::ln_fwd_class(dim, elem_bytes_of(dtype), x, weight, bias, y);
+  const RowClass k = norm_dispatch::ln_fwd_class(dim, dtype_bytes(dtype), x, weight, bias, y);
   if (int e = accept_row(k, dim, "swish_layer_norm_fwd")) return e;
   DISPATCH_DTYPE(dtype, NW(k, ln_fwd<bf16_t, true>(k, x, weight, bias, y, mean, rstd, rows, dim, eps, st)),
                  NW(k, ln_fwd<f16_t, true>(k, x, weight, bias, y, mean, rstd, rows, dim, eps, st)),
@@ -122,7 +123,7 @@ int hstu_swish_layer_norm_bwd(const void* dy, const void* x, const void* weight,
     return HSTU_OK;
   }
   if (!dy || !x || !weight || !bias || !mean || !rstd || !dx || !partial_ws) return set_error(HSTU_EINVAL, "swish_layer_norm_bwd: NULL tensor");
-  const RowClass k = norm_dispatch::ln_bwd_class(dim, elem_bytes_of(dtype), dy, x, weight, bias, nullptr, dx);
+  const RowClass k = norm_dispatch::ln_bwd_class(dim, dtype_bytes(dtype), dy, x, weight, bias, nullptr, dx);
   if (int e = accept_row(k, dim, "swish_layer_norm_bwd")) return e;
   DISPATCH_DTYPE(dtype, NW(k, ln_bwd<bf16_t, true>(k, dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, nullptr, st, bias)),
                  NW(k, ln_bwd<f16_t, true>(k, dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, nullptr, st, bias)),
@@ -151,7 +152,7 @@ int hstu_norm_mul_silu_fwd(const void* attn, const void* u, int64_t u_row_stride
   if (rows == 0) return HSTU_OK;
   if (!attn || !u || !weight || !bias || !y) return set_error(HSTU_EINVAL, "norm_mul_fwd: NULL tensor");
   hipStream_t st = (hipStream_t)stream;
-  const RowClass k = norm_dispatch::nm_fwd_class(heads, head_dim, elem_bytes_of(dtype), group_norm != 0, attn, u, u_row_stride, weight, bias, y);
+  const RowClass k = norm_dispatch::nm_fwd_class(heads, head_dim, dtype_bytes(dtype), group_norm != 0, attn, u, u_row_stride, weight, bias, y);
   if (int e = accept_row(k, heads * head_dim, "norm_mul_fwd")) return e;
 #define NM_FWD(T) (k.wide ? nw4::nm_fwd<T>(k, attn, u, weight, bias, y, mean, rstd, rows, heads, head_dim, eps, group_norm, concat_ux, nw4::make_drop_ctx(dropout_ratio, seed), u_row_stride, silu, st) \
                       : nw1::nm_fwd<T>(k, attn, u, weight, bias, y, mean, rstd, rows, heads, head_dim, eps, group_norm, concat_ux, nw1::make_drop_ctx(dropout_ratio, seed), u_row_stride, silu, st))
@@ -202,7 +203,7 @@ int hstu_norm_mul_silu_bwd(const void* dy, const void* attn, const void* u, int6
   }
   if (!dy || !attn || !u || !weight || !bias || !mean || !rstd || !dattn || !du || !partial_ws)
     return set_error(HSTU_EINVAL, "norm_mul_bwd: NULL tensor");
-  const RowClass k = norm_dispatch::nm_bwd_class(heads, head_dim, elem_bytes_of(dtype), group_norm != 0, dy, attn, u, u_row_stride, weight, bias,
+  const RowClass k = norm_dispatch::nm_bwd_class(heads, head_dim, dtype_bytes(dtype), group_norm != 0, dy, attn, u, u_row_stride, weight, bias,
                                                  dattn, du, du_row_stride);
   if (int e = accept_row(k, heads * head_dim, "norm_mul_bwd")) return e;
 #define NM_BWD(T) (k.wide ? nw4::nm_bwd<T>(k, dy, attn, u, weight, bias, mean, rstd, dattn, du, dweight, dbias, partial_ws, rows, heads, head_dim, group_norm, concat_ux, nw4::make_drop_ctx(dropout_ratio, seed), u_row_stride, du_row_stride, silu, st) \
@@ -214,7 +215,7 @@ int hstu_norm_mul_silu_bwd(const void* dy, const void* attn, const void* u, int6
 int hstu_silu_fwd(const void* in, void* out, int64_t rows, int32_t cols, int64_t in_row_stride, int64_t out_row_stride,
                   int dtype, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const bool vk = norm_dispatch::silu_vector(elem_bytes_of(dtype), cols, nullptr, in, out, 0, in_row_stride, out_row_stride);
+  const bool vk = norm_dispatch::silu_vector(dtype_bytes(dtype), cols, nullptr, in, out, 0, in_row_stride, out_row_stride);
   DISPATCH_DTYPE(dtype, (silu_launch<bf16_t, false>(vk, nullptr, in, out, rows, cols, 0, in_row_stride, out_row_stride, st)),
                  (silu_launch<f16_t, false>(vk, nullptr, in, out, rows, cols, 0, in_row_stride, out_row_stride, st)),
                  (silu_launch<float, false>(vk, nullptr, in, out, rows, cols, 0, in_row_stride, out_row_stride, st)));
@@ -223,7 +224,7 @@ int hstu_silu_fwd(const void* in, void* out, int64_t rows, int32_t cols, int64_t
 int hstu_silu_bwd(const void* dout, const void* in, void* din, int64_t rows, int32_t cols, int64_t dout_row_stride,
                   int64_t in_row_stride, int64_t din_row_stride, int dtype, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const bool vk = norm_dispatch::silu_vector(elem_bytes_of(dtype), cols, dout, in, din, dout_row_stride, in_row_stride, din_row_stride);
+  const bool vk = norm_dispatch::silu_vector(dtype_bytes(dtype), cols, dout, in, din, dout_row_stride, in_row_stride, din_row_stride);
   DISPATCH_DTYPE(dtype, (silu_launch<bf16_t, true>(vk, dout, in, din, rows, cols, dout_row_stride, in_row_stride, din_row_stride, st)),
                  (silu_launch<f16_t, true>(vk, dout, in, din, rows, cols, dout_row_stride, in_row_stride, din_row_stride, st)),
                  (silu_launch<float, true>(vk, dout, in, din, rows, cols, dout_row_stride, in_row_stride, din_row_stride, st)));
@@ -234,7 +235,7 @@ int hstu_l2_norm_fwd(const void* x, void* y, int64_t rows, int32_t dim, float ep
   if (rows > 0 && (!x || !y)) return set_error(HSTU_EINVAL, "hstu_l2_norm_fwd: x and y must be non-NULL");
   hipStream_t st = (hipStream_t)stream;
   if (rows == 0) return HSTU_OK;
-  const RowClass k = norm_dispatch::l2_class(dim, elem_bytes_of(dtype), x, nullptr, y);
+  const RowClass k = norm_dispatch::l2_class(dim, dtype_bytes(dtype), x, nullptr, y);
   if (int e = accept_row(k, dim, "l2_norm")) return e;
   DISPATCH_DTYPE(dtype, NW(k, l2_launch<bf16_t, false>(k, x, nullptr, y, rows, dim, eps, st)),
                  NW(k, l2_launch<f16_t, false>(k, x, nullptr, y, rows, dim, eps, st)),
@@ -245,7 +246,7 @@ int hstu_l2_norm_bwd(const void* dy, const void* x, void* dx, int64_t rows, int3
   if (rows > 0 && (!x || !dy || !dx)) return set_error(HSTU_EINVAL, "hstu_l2_norm_bwd: dy, x and dx must be non-NULL");
   hipStream_t st = (hipStream_t)stream;
   if (rows == 0) return HSTU_OK;
-  const RowClass k = norm_dispatch::l2_class(dim, elem_bytes_of(dtype), x, dy, dx);
+  const RowClass k = norm_dispatch::l2_class(dim, dtype_bytes(dtype), x, dy, dx);
   if (int e = accept_row(k, dim, "l2_norm")) return e;
   DISPATCH_DTYPE(dtype, NW(k, l2_launch<bf16_t, true>(k, x, dy, dx, rows, dim, eps, st)),
                  NW(k, l2_launch<f16_t, true>(k, x, dy, dx, rows, dim, eps, st)),

@@ -107,7 +107,7 @@ int hstu_add_ts_pos_emb_fwd(const void* x, void* out, const void* seq_offsets, c
     return set_error(HSTU_EINVAL, "hstu_add_ts_pos_emb_fwd: bad sizes");
   if (time_bucket_fn != 0 && time_bucket_fn != 1)
     return set_error(HSTU_EINVAL, "hstu_add_ts_pos_emb_fwd: time_bucket_fn must be 0 (sqrt) or 1 (log)");
-  const int es = dtype == HSTU_DTYPE_F32 ? 4 : 2;
+  const int es = dtype_bytes(dtype);
   if ((dim * es) % 16 || (((uintptr_t)x | (uintptr_t)out) & 15))
     return set_error(HSTU_EINVAL, "hstu_add_ts_pos_emb_fwd: rows must be 16-byte multiples and 16-byte aligned");
   if (batch == 0) return HSTU_OK;

@@ -301,8 +301,7 @@ static int fill_action_args(ActionArgs* a, const int64_t* weights, int num_types
 
 static int check_sizes(const char* what, int64_t total_a, int64_t total_b, int batch, int dim, int dtype, int index_dtype) {
   if (total_a < 0 || total_b < 0 || batch < 0 || dim < 1) return set_error(HSTU_EINVAL, "%s: negative size / empty rows", what);
-  if (dtype != HSTU_DTYPE_BF16 && dtype != HSTU_DTYPE_F16 && dtype != HSTU_DTYPE_F32)
-    return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32", what);
+  if (!is_float_dtype(dtype)) return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32", what);
   if (index_dtype != HSTU_INDEX_I32 && index_dtype != HSTU_INDEX_I64)
     return set_error(HSTU_EINVAL, "%s: offsets must be int32 or int64", what);
   if (total_a > INT32_MAX || total_b > INT32_MAX || total_a + total_b > INT32_MAX)

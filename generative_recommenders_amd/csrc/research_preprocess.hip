@@ -281,7 +281,6 @@ int rating_groups(const Dims& d) {
   return g < 1 ? 1 : (int)g;
 }
 
-size_t align256(size_t n) { return (n + 255) / 256 * 256; }
 size_t pos_partial_bytes(const Dims& d) { return align256((size_t)bwd_groups(d) * d.Nout * d.Do * sizeof(float)); }
 size_t rating_partial_bytes(const Dims& d) {
   return d.layout == HSTU_PREPROCESS_PLAIN ? 0 : align256((size_t)rating_groups(d) * d.R * d.Dr * sizeof(float));
@@ -456,8 +455,6 @@ int rating_dispatch(const Dims& d, const PreArgs& a, int V, int out_dtype, const
   PRE_BY_DTYPE(rating_by_vec, V, d, a, g, partial, st)
 }
 
-size_t dtype_size(int dtype) { return dtype == HSTU_DTYPE_F32 ? 4 : 2; }
-
 }  // namespace
 }  // namespace hstu
 
@@ -490,7 +487,7 @@ int hstu_input_preprocess_fwd(const int64_t* past_ids, const void* past_embeddin
   if (layout != HSTU_PREPROCESS_PLAIN && (!ratings || !rating_table))
     return set_error(HSTU_EINVAL, "%s: the rated layouts need ratings and the rating table", what);
   const PreArgs a = make_args(d, past_ids, ratings, rating_index_dtype, dropout_ratio, seed);
-  const int V = pick_vec(d, dtype_size(emb_dtype), dtype_size(out_dtype), {past_embeddings}, {pos_table, rating_table, out});
+  const int V = pick_vec(d, dtype_bytes(emb_dtype), dtype_bytes(out_dtype), {past_embeddings}, {pos_table, rating_table, out});
   return fwd_dispatch(d, a, V, emb_dtype, out_dtype, past_embeddings, pos_table, rating_table, out, valid_mask,
                       (hipStream_t)stream);
 }
@@ -520,7 +517,7 @@ int hstu_input_preprocess_bwd(const void* d_out, const int64_t* past_ids, const 
   const PreArgs a = make_args(d, past_ids, ratings, rating_index_dtype, dropout_ratio, seed);
   float* pos_partial = d_pos_table ? (float*)workspace : nullptr;
   float* rating_partial = d_rating_table ? (float*)((char*)workspace + pos_partial_bytes(d)) : nullptr;
-  const int V = pick_vec(d, dtype_size(emb_dtype), dtype_size(out_dtype), {d_past_embeddings}, {d_out, workspace});
+  const int V = pick_vec(d, dtype_bytes(emb_dtype), dtype_bytes(out_dtype), {d_past_embeddings}, {d_out, workspace});
   if (d_past_embeddings || d_pos_table) {
     if (int e = bwd_dispatch(d, a, V, emb_dtype, out_dtype, d_out, d_past_embeddings, pos_partial, st)) return e;
   }

@@ -13,7 +13,9 @@
 // one workgroup column per chunk, each sweeping the whole row for the norm's two row sums (a row is read once per chunk).
 // Every sum over rows is a per-lane sum in row order, a fixed-order sum over the workgroup's waves through LDS, one partial
 // per workgroup in the workspace and a fixed-order finish kernel: no float atomics, bit-identical run to run.
-#include "hstu_common.cuh"
+// Pieces, wave sums and the sum over the waves are row_pass.cuh's; the grid rule and the backward's finish kernel
+// (launch_partial_col_sums, aux_ops.hip) are capi_internal.h's.
+#include "row_pass.cuh"
 #include "capi_internal.h"
 #include "norm_dispatch.h"
 
@@ -60,68 +62,6 @@ __global__ __launch_bounds__(256) void time_features_kernel(const int64_t* t, co
     const int64_t row = i / nf;
     out[i] = time_feature(t[row], period_units, units_per_period, (int)(i - row * nf));
   }
-}
-
-// ------------------------------------------------------------------ pieces
-template <typename T, int VEC>
-HSTU_DEV void load_piece(float (&v)[VEC], const T* p, bool ok) {
-  if (!ok) {
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) v[i] = 0.f;
-    return;
-  }
-  if constexpr (VEC == 1) {
-    v[0] = (float)p[0];
-  } else {
-    static_assert(VEC * sizeof(T) == 16, "a 16-byte piece");
-    typedef T tv __attribute__((ext_vector_type(VEC)));
-    const tv t = __builtin_bit_cast(tv, *reinterpret_cast<const u32x4*>(p));
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) v[i] = (float)t[i];
-  }
-}
-
-template <typename T, int VEC>
-HSTU_DEV void store_piece(const float (&v)[VEC], T* p) {
-  if constexpr (VEC == 1) {
-    p[0] = (T)v[0];
-  } else {
-    typedef T tv __attribute__((ext_vector_type(VEC)));
-    tv t;
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) t[i] = (T)v[i];
-    __builtin_nontemporal_store(__builtin_bit_cast(u32x4, t), reinterpret_cast<u32x4*>(p));
-  }
-}
-
-// VEC consecutive fp32 parameters (16-byte loads when the row is read in pieces: the class asks for their alignment)
-template <int VEC>
-HSTU_DEV void load_param(float (&v)[VEC], const float* p, bool ok) {
-  if (!ok) {
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) v[i] = 0.f;
-    return;
-  }
-  if constexpr (VEC == 1) {
-    v[0] = p[0];
-  } else {
-#pragma unroll
-    for (int q = 0; q < VEC / 4; ++q) {
-      const f32x4 t = *reinterpret_cast<const f32x4*>(p + 4 * q);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[4 * q + i] = t[i];
-    }
-  }
-}
-
-HSTU_DEV float tl_wave_sum(float x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
-}
-
-HSTU_DEV float lane_value(float v, int j) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j));
 }
 
 struct TlFwdArgs {
@@ -219,7 +159,7 @@ __global__ __launch_bounds__(kTlThreads) void time_ln_fwd_kernel(const TlFwdArgs
 #pragma unroll
       for (int i = 0; i < VEC; ++i) s += zv[k][i];
     }
-    const float mean = tl_wave_sum(s) / dim;
+    const float mean = wave_sum(s) / dim;
     float q = 0.f;
 #pragma unroll
     for (int k = 0; k < MC; ++k) {
@@ -229,7 +169,7 @@ __global__ __launch_bounds__(kTlThreads) void time_ln_fwd_kernel(const TlFwdArgs
         for (int i = 0; i < VEC; ++i) { const float d = zv[k][i] - mean; q += d * d; }
       }
     }
-    const float rstd = 1.0f / sqrtf(tl_wave_sum(q) / dim + a.eps);
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / dim + a.eps);
 #pragma unroll
     for (int k = 0; k < MC; ++k) {
       const int c = (k * 64 + lane) * VEC;
@@ -245,7 +185,7 @@ __global__ __launch_bounds__(kTlThreads) void time_ln_fwd_kernel(const TlFwdArgs
 #pragma unroll
           for (int i = 0; i < VEC; ++i) o[i] = (zv[k][i] - mean) * rstd * gv[i] + hv[i];
         }
-        store_piece<T, VEC>(o, (T*)a.y + row * dim + c);
+        store_piece<T, VEC, true>(o, (T*)a.y + row * dim + c);
       }
     }
     if (lane == 0) {
@@ -256,22 +196,6 @@ __global__ __launch_bounds__(kTlThreads) void time_ln_fwd_kernel(const TlFwdArgs
 }
 
 // ------------------------------------------------------------------ backward
-// sum over the workgroup's waves of one per-lane array of column partials -> out[c0 .. c0 + 64 VEC) (columns < dim)
-template <int VEC>
-HSTU_DEV void block_sum_cols(const float (&acc)[VEC], float* lds, float* out, int c0, int dim) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) lds[wave * 64 * VEC + lane * VEC + i] = acc[i];
-  __syncthreads();
-  for (int c = threadIdx.x; c < 64 * VEC; c += kTlThreads) {
-    float s = 0.f;
-#pragma unroll
-    for (int w2 = 0; w2 < kTlWaves; ++w2) s += lds[w2 * 64 * VEC + c];
-    if (c0 + c < dim) out[c0 + c] = s;
-  }
-  __syncthreads();
-}
-
 // one piece of a row: xhat of the recomputed z and the gradient entering it, dxh = dy ln_w (zeros in a lane past the row)
 template <int VEC, int NF>
 HSTU_DEV void piece_terms(float (&z)[VEC], const float (&dyv)[VEC], const float (&bv)[VEC], const float (&wv)[NF][VEC],
@@ -339,7 +263,7 @@ __global__ __launch_bounds__(kTlThreads) void time_ln_bwd_kernel(const TlBwdArgs
         s2 += g;
       }
     }
-    const float c1 = tl_wave_sum(s1) / dim, c2 = tl_wave_sum(s2) / dim;
+    const float c1 = wave_sum(s1) / dim, c2 = wave_sum(s2) / dim;
     if (ok) {
       float o[VEC];
 #pragma unroll
@@ -352,61 +276,24 @@ __global__ __launch_bounds__(kTlThreads) void time_ln_bwd_kernel(const TlBwdArgs
         for (int j = 0; j < NF; ++j)
           if (j < nf) dw[j][i] += tf[j] * o[i];
       }
-      store_piece<T, VEC>(o, (T*)a.dz + row * dim + c);
+      store_piece<T, VEC, true>(o, (T*)a.dz + row * dim + c);
     }
   }
   float* prow = a.partial + (int64_t)blockIdx.x * (3 + nf) * dim;
-  block_sum_cols<VEC>(dg, lds, prow, c0, dim);
-  block_sum_cols<VEC>(dh, lds, prow + dim, c0, dim);
-  block_sum_cols<VEC>(db, lds, prow + 2 * (int64_t)dim, c0, dim);
+  block_sum_cols<VEC, kTlWaves>(dg, lds, prow, c0, dim);
+  block_sum_cols<VEC, kTlWaves>(dh, lds, prow + dim, c0, dim);
+  block_sum_cols<VEC, kTlWaves>(db, lds, prow + 2 * (int64_t)dim, c0, dim);
 #pragma unroll
   for (int j = 0; j < NF; ++j)
-    if (j < nf) block_sum_cols<VEC>(dw[j], lds, prow + (int64_t)(3 + j) * dim, c0, dim);
-}
-
-// Column sums of the workgroups' partials (nparts rows of pstride = (3 + nf) dim floats): 16 columns per block, thread
-// (r, cc) adds rows r, r + 16, .. of column cc in order, then the 16 sums are added in order.
-__global__ __launch_bounds__(256) void time_ln_bwd_finish_kernel(const float* partial, int nparts, int64_t pstride, int dim,
-                                                                 float* dln_w, float* dln_b, float* db, float* dwt) {
-  __shared__ float red[16][17];
-  const int cc = threadIdx.x & 15, r = threadIdx.x >> 4;
-  const int64_t col = (int64_t)blockIdx.x * 16 + cc;
-  float s = 0.f;
-  if (col < pstride)
-    for (int i = r; i < nparts; i += 16) s += partial[(int64_t)i * pstride + col];
-  red[r][cc] = s;
-  __syncthreads();
-  if (r == 0 && col < pstride) {
-    float tot = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) tot += red[k][cc];
-    if (col < dim) dln_w[col] = tot;
-    else if (col < 2 * (int64_t)dim) dln_b[col - dim] = tot;
-    else if (col < 3 * (int64_t)dim) db[col - 2 * (int64_t)dim] = tot;
-    else dwt[col - 3 * (int64_t)dim] = tot;
-  }
+    if (j < nf) block_sum_cols<VEC, kTlWaves>(dw[j], lds, prow + (int64_t)(3 + j) * dim, c0, dim);
 }
 
 // ------------------------------------------------------------------ host side
-// the workgroups that are resident at once (every wave then walks the same number of rows), at most kTlMaxBlocks,
-// divided among `cols` workgroup columns
-template <typename K>
-static int tl_row_blocks(K kernel, int64_t rows, int cols) {
-  int64_t nb = (rows + kTlWaves - 1) / kTlWaves;
-  if (nb > kTlMaxBlocks) nb = kTlMaxBlocks;
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kTlThreads, 0) == hipSuccess && per_cu >= 1) {
-    int64_t resident = (int64_t)per_cu * cu_count() / cols;
-    if (resident < 1) resident = 1;
-    if (resident < nb) nb = resident;
-  }
-  return (int)(nb < 1 ? 1 : nb);
-}
-
+// (grids: the resident one, at most kTlMaxBlocks; the backward's is divided among its workgroup columns)
 template <typename T, int VEC, int MC, int NF>
 static int fwd_go(const TlFwdArgs& a, hipStream_t st) {
   auto kernel = time_ln_fwd_kernel<T, VEC, MC, NF>;
-  hipLaunchKernelGGL(kernel, dim3(tl_row_blocks(kernel, a.rows, 1)), dim3(kTlThreads), 0, st, a);
+  hipLaunchKernelGGL(kernel, dim3(resident_row_blocks(kernel, kTlThreads, 0, a.rows, kTlWaves, kTlMaxBlocks)), dim3(kTlThreads), 0, st, a);
   return check_launch("hstu_time_ln_fwd");
 }
 
@@ -428,13 +315,11 @@ static int bwd_go(const TlBwdArgs& a, float* dln_w, float* dln_b, float* db, flo
   const char* who = "hstu_time_ln_bwd";
   auto kernel = time_ln_bwd_kernel<T, VEC, NF>;
   const int nch = (a.dim + 64 * VEC - 1) / (64 * VEC);
-  const int nb = tl_row_blocks(kernel, a.rows, nch);
+  const int nb = resident_row_blocks(kernel, kTlThreads, 0, a.rows, kTlWaves, kTlMaxBlocks, nch);
   hipLaunchKernelGGL(kernel, dim3(nb, nch), dim3(kTlThreads), 0, st, a);
   if (int e = check_launch(who)) return e;
   const int64_t pstride = (int64_t)(3 + a.nf) * a.dim;
-  hipLaunchKernelGGL(time_ln_bwd_finish_kernel, dim3((unsigned)((pstride + 15) / 16)), dim3(256), 0, st, a.partial, nb, pstride,
-                     a.dim, dln_w, dln_b, db, dwt);
-  return check_launch(who);
+  return launch_partial_col_sums(a.partial, nb, pstride, {{dln_w, a.dim}, {dln_b, a.dim}, {db, a.dim}, {dwt, (int64_t)a.nf * a.dim}}, who, st);
 }
 
 // the backward's lanes hold one chunk whatever the row's width: only the piece width of the class picks its instance
@@ -448,8 +333,7 @@ static int bwd_pick(const TlBwdArgs& a, const norm_dispatch::RowClass& k, float*
 
 // max_periods: what the row pass holds in registers (HSTU_TIME_LN_MAX_PERIODS); the feature kernel alone takes any number
 static int check_common(const char* who, int num_periods, int max_periods, int dim, int64_t rows, int dtype) {
-  if (dtype != HSTU_DTYPE_BF16 && dtype != HSTU_DTYPE_F16 && dtype != HSTU_DTYPE_F32)
-    return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32 (got code %d)", who, dtype);
+  if (!is_float_dtype(dtype)) return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32 (got code %d)", who, dtype);
   if (num_periods < 1 || num_periods > max_periods)
     return set_error(HSTU_EINVAL, "%s: num_periods must be in [1, %d] (got %d)", who, max_periods, num_periods);
   if (rows < 0) return set_error(HSTU_EINVAL, "%s: negative rows", who);
@@ -462,8 +346,6 @@ static int accept_class(const char* who, const norm_dispatch::RowClass& k, int d
     return set_error(HSTU_EUNSUPPORTED, "%s: dim %d exceeds the %d supported with this alignment", who, dim, k.limit);
   return HSTU_OK;
 }
-
-static int elem_bytes_of(int dtype) { return dtype == HSTU_DTYPE_F32 ? 4 : 2; }
 
 }  // namespace
 }  // namespace hstu
@@ -501,7 +383,7 @@ int hstu_time_ln_fwd(const void* z0, const int64_t* timestamps, const float* per
   if (int e = check_common(who, num_periods, HSTU_TIME_LN_MAX_PERIODS, dim, rows, dtype)) return e;
   if (!period_units || !units_per_period || !b || !wt || !ln_weight || !ln_bias)
     return set_error(HSTU_EINVAL, "%s: the periods, b, wt, ln_weight and ln_bias must be non-NULL", who);
-  const int eb = elem_bytes_of(dtype);
+  const int eb = dtype_bytes(dtype);
   if ((((uintptr_t)z0 | (uintptr_t)y) & (eb - 1)) || ((uintptr_t)timestamps & 7) ||
       (((uintptr_t)period_units | (uintptr_t)units_per_period | (uintptr_t)b | (uintptr_t)wt | (uintptr_t)ln_weight |
         (uintptr_t)ln_bias | (uintptr_t)mean | (uintptr_t)rstd) & 3))
@@ -529,7 +411,7 @@ int hstu_time_ln_bwd(const void* dy, const void* z0, const int64_t* timestamps, 
   if (!period_units || !units_per_period || !b || !wt || !ln_weight)
     return set_error(HSTU_EINVAL, "%s: the periods, b, wt and ln_weight must be non-NULL", who);
   if (!dln_weight || !dln_bias || !db || !dwt) return set_error(HSTU_EINVAL, "%s: dln_weight, dln_bias, db and dwt are required", who);
-  const int eb = elem_bytes_of(dtype);
+  const int eb = dtype_bytes(dtype);
   if ((((uintptr_t)dy | (uintptr_t)z0 | (uintptr_t)dz) & (eb - 1)) || ((uintptr_t)timestamps & 7) || ((uintptr_t)workspace & 15) ||
       (((uintptr_t)period_units | (uintptr_t)units_per_period | (uintptr_t)b | (uintptr_t)wt | (uintptr_t)ln_weight |
         (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)dln_weight | (uintptr_t)dln_bias | (uintptr_t)db | (uintptr_t)dwt) & 3))

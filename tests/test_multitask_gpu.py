@@ -213,6 +213,49 @@ def test_two_runs_are_bit_identical():
         assert torch.equal(a[k], b[k]), k
 
 
+def test_finish_kernel_adds_the_partial_rows_in_the_documented_order():
+    """The backward through the C ABI with a workspace this test owns: the workgroups' partial rows, read back from it and
+    added in numpy fp32 in the finish kernel's order, give the returned gradients bit for bit.  150 rows = 38 workgroups of 4
+    rows (below any grid cap): thread r < 6 adds three partial rows, the others two.  Partial row of dim 72, 3 tasks:
+    [dW 216 | dg 72 | db 72 | dc 3 | 5 unused] = 368 floats, dc ends inside the last block of 16 columns."""
+    from generative_recommenders_amd import _lib as L
+    from generative_recommenders_amd.ops import _launch
+
+    rows, dim, nb, T = 150, 72, 2, 3
+    inp = _op_inputs(torch.float32, dim, (nb, T - nb), rows, None, True)
+    x, lw, lb, w = inp["xd"], inp["lw"].to(DEV), inp["lb"].to(DEV), inp["w"].to(DEV)
+    labels, weights, r = inp["labels"].to(DEV), inp["weights"].to(DEV), inp["r"].to(DEV)
+    logits, _, mean, rstd, _, wsum = _launch.multitask_head_fwd(x, lw, lb, 1e-5, w, inp["c"].to(DEV), labels, weights, nb, 0.3)
+    grad_loss = torch.linspace(0.5, 1.5, T, device=DEV)
+    lib = L.lib()
+    nbytes = lib.hstu_multitask_head_workspace_bytes(dim, T)
+    nparts, pstride = -(-rows // 4), (T + 2) * dim + 8
+    assert (nparts, pstride) == (38, 368) and nbytes >= nparts * pstride * 4
+    ws = torch.full((nbytes // 4,), float("nan"), dtype=torch.float32, device=DEV)
+    dx = torch.empty_like(x)
+    dw, dc = torch.empty(T, dim, device=DEV), torch.empty(T, device=DEV)
+    dg, db = torch.empty(dim, device=DEV), torch.empty(dim, device=DEV)
+    L.check(lib.hstu_multitask_head_bwd(grad_loss.data_ptr(), r.data_ptr(), x.data_ptr(), x.stride(0), lw.data_ptr(), lb.data_ptr(),
+                                        w.data_ptr(), labels.data_ptr(), weights.data_ptr(), logits.data_ptr(), mean.data_ptr(),
+                                        rstd.data_ptr(), wsum.data_ptr(), dx.data_ptr(), dx.stride(0), dw.data_ptr(), dc.data_ptr(),
+                                        dg.data_ptr(), db.data_ptr(), ws.data_ptr(), rows, dim, T, nb, 0.3,
+                                        L.torch_dtype_code(torch.float32), L.current_stream_ptr(x.device)))
+    torch.cuda.synchronize()
+    partial = ws[:nparts * pstride].view(nparts, pstride).cpu().numpy()
+    assert np.isfinite(partial).all() and np.isnan(ws[nparts * pstride:].cpu().numpy()).all()     # exactly 38 partial rows
+    shares = np.zeros((16, pstride), dtype=np.float32)
+    for i in range(nparts):               # thread (r, cc): rows r, r + 16, .. in order into one running sum
+        shares[i % 16] += partial[i]
+    total = np.zeros(pstride, dtype=np.float32)
+    for k in range(16):                   # then the 16 sums in index order
+        total += shares[k]
+    assert total.dtype == np.float32
+    for name, got, lo, n in (("dw", dw, 0, T * dim), ("dg", dg, T * dim, dim), ("db", db, (T + 1) * dim, dim), ("dc", dc, (T + 2) * dim, T)):
+        g = got.cpu().numpy().reshape(-1)
+        assert g.size == n and np.count_nonzero(g) > 0, name
+        assert np.array_equal(g.view(np.uint32), total[lo:lo + n].view(np.uint32)), name
+
+
 def test_no_rows_gives_zero_losses_and_zero_gradients():
     inp = _op_inputs(torch.bfloat16, 512, (3, 2), 0, None, True)
     got = _run_op(inp, torch.bfloat16)

@@ -174,6 +174,50 @@ def test_two_backward_calls_give_bit_identical_reductions(path):
         assert torch.isfinite(a.float()).all() and torch.equal(a, bb)
 
 
+def test_finish_kernel_adds_the_partial_rows_in_the_documented_order():
+    """The backward through the C ABI with a workspace this test owns: the workgroups' partial rows, read back from it and
+    added in numpy fp32 in the finish kernel's order, give the returned column sums bit for bit.  150 rows = 38 workgroups of
+    4 rows (below any grid cap): thread r < 6 adds three partial rows, the others two.  Partial row of dim 72, 2 periods:
+    [dln_w 72 | dln_b 72 | db 72 | dwt 4 x 72] = 504 floats, the last block of 16 columns half full."""
+    from generative_recommenders_amd import _lib as L
+    from generative_recommenders_amd.ops import _launch
+
+    rows, dim, nf = 150, 72, 4
+    g = torch.Generator().manual_seed(72)
+    z0, dy = torch.randn(rows, dim, generator=g).to(DEV), torch.randn(rows, dim, generator=g).to(DEV)
+    t = torch.randint(0, 2_000_000_000, (rows,), generator=g).to(DEV)
+    pu, upp = _t(np.asarray([3600, 86400], dtype=np.float32)), _t(np.asarray([24, 7], dtype=np.float32))
+    b, wt = (0.1 * torch.randn(dim, generator=g)).to(DEV), (0.1 * torch.randn(nf, dim, generator=g)).to(DEV)
+    lw, lb = (1 + 0.1 * torch.randn(dim, generator=g)).to(DEV), (0.1 * torch.randn(dim, generator=g)).to(DEV)
+    _, mean, rstd = _launch.time_ln_fwd(z0, t, pu, upp, b, wt, lw, lb, 1e-5)
+    lib = L.lib()
+    nbytes = lib.hstu_time_ln_workspace_bytes(dim, nf // 2)
+    nparts, pstride = -(-rows // 4), (3 + nf) * dim
+    assert (nparts, pstride) == (38, 504) and nbytes >= nparts * pstride * 4
+    ws = torch.full((nbytes // 4,), float("nan"), dtype=torch.float32, device=DEV)
+    dz = torch.empty_like(z0)
+    dln_w, dln_b, db = (torch.empty(dim, device=DEV) for _ in range(3))
+    dwt = torch.empty(nf, dim, device=DEV)
+    L.check(lib.hstu_time_ln_bwd(dy.data_ptr(), z0.data_ptr(), t.data_ptr(), pu.data_ptr(), upp.data_ptr(), nf // 2, b.data_ptr(),
+                                 wt.data_ptr(), lw.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dz.data_ptr(), dln_w.data_ptr(),
+                                 dln_b.data_ptr(), db.data_ptr(), dwt.data_ptr(), ws.data_ptr(), rows, dim,
+                                 L.torch_dtype_code(torch.float32), L.current_stream_ptr(z0.device)))
+    torch.cuda.synchronize()
+    partial = ws[:nparts * pstride].view(nparts, pstride).cpu().numpy()
+    assert np.isfinite(partial).all() and np.isnan(ws[nparts * pstride:].cpu().numpy()).all()     # exactly 38 partial rows
+    shares = np.zeros((16, pstride), dtype=np.float32)
+    for i in range(nparts):               # thread (r, cc): rows r, r + 16, .. in order into one running sum
+        shares[i % 16] += partial[i]
+    total = np.zeros(pstride, dtype=np.float32)
+    for k in range(16):                   # then the 16 sums in index order
+        total += shares[k]
+    assert total.dtype == np.float32
+    for name, got, lo, n in (("dln_w", dln_w, 0, dim), ("dln_b", dln_b, dim, dim), ("db", db, 2 * dim, dim), ("dwt", dwt, 3 * dim, nf * dim)):
+        v = got.cpu().numpy().reshape(-1)
+        assert v.size == n and np.count_nonzero(v) > 0, name
+        assert np.array_equal(v.view(np.uint32), total[lo:lo + n].view(np.uint32)), name
+
+
 def test_a_strided_input_is_handled():
     """x as a column slice of a wider buffer and as every other row: the same values as from a contiguous copy"""
     from generative_recommenders_amd.ops.timestamp_layer_norm import timestamp_layer_norm
