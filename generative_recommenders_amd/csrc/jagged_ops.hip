@@ -10,6 +10,7 @@
 // ops/cpp/{complete_cumsum,expand_1d_jagged_to_dense,concat_1d_jagged_jagged}.cu.
 #include "hstu_common.cuh"
 #include "capi_internal.h"
+#include "jagged_dispatch.h"
 
 namespace hstu {
 
@@ -166,14 +167,7 @@ __global__ void concat_1d_kernel(const E* vl, const void* ol, const E* vr, const
   for (int i = threadIdx.x; i < la + lb; i += blockDim.x) out[a0 + b0 + i] = i < la ? vl[a0 + i] : vr[b0 + i - la];
 }
 
-static int pick_vec(int row_bytes, const void* a, const void* b, const void* c) {
-  uintptr_t bits = (uintptr_t)row_bytes | (uintptr_t)a | (uintptr_t)b | (uintptr_t)c;
-  if ((bits & 15) == 0) return 16;
-  if ((bits & 7) == 0) return 8;
-  if ((bits & 3) == 0) return 4;
-  if ((bits & 1) == 0) return 2;
-  return 1;
-}
+using jagged_dispatch::pick_vec;   // jagged_dispatch.h: host-only, tested on the CPU
 
 template <bool SPLIT>
 static int launch_concat_split(char* left, char* right, char* comb, const void* off_l, const void* off_r,

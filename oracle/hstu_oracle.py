@@ -139,7 +139,7 @@ def split_2D_jagged(
     for b in range(B):
         ll = int(offsets_left[b + 1] - offsets_left[b])
         lr = int(offsets_right[b + 1] - offsets_right[b])
-        n = n_prefix_to_right
+        n = min(n_prefix_to_right, lr)      # what concat's r[:n] puts in front when the right side is shorter
         seg = values[pos : pos + ll + lr]
         rights.append(seg[:n])
         lefts.append(seg[n : n + ll])

@@ -133,6 +133,47 @@ def test_1d_helpers():
     assert c.cpu().tolist() == [7, 1, 2, 3, 8, 9]
 
 
+@pytest.mark.parametrize("max_len", [1, 64, 65, 200])          # 64 | 65: one | two blocks along the row
+@pytest.mark.parametrize("vdtype", [torch.int32, torch.int64])
+@pytest.mark.parametrize("odtype", [torch.int32, torch.int64])
+def test_expand_1d_jagged_to_dense_vs_oracle(max_len, vdtype, odtype):
+    lengths = np.array([0, 1, max_len, max_len + 7, 3, 70])      # empty; its one value repeated; exact; longer than max_len
+    off = O.complete_cumsum(lengths)
+    rng = np.random.default_rng(max_len)
+    hi = 2 ** 31 - 1 if vdtype == torch.int32 else 2 ** 62
+    vals = torch.from_numpy(rng.integers(-hi, hi, size=int(off[-1]))).to(vdtype)
+    got = _jt().expand_1d_jagged_to_dense(vals.to(DEV), torch.from_numpy(off).to(odtype).to(DEV), max_len)
+    ref = O.expand_1d_jagged_to_dense(vals.numpy(), off, max_len)
+    assert got.dtype == vdtype and got.shape == ref.shape
+    assert np.array_equal(got.cpu().numpy(), ref)
+    assert not ref[0].any() and (ref[1] == ref[1, 0]).all()
+
+
+@pytest.mark.parametrize("vdtype", [torch.int32, torch.int64])
+def test_concat_1d_jagged_jagged_vs_oracle(vdtype):
+    # more than 128 elements in one user (the block-stride loop), 128 and 129 exactly, empty on either side and on both
+    ll = np.array([100, 0, 5, 0, 128, 300, 1])
+    lr = np.array([90, 7, 0, 0, 1, 0, 127])
+    rng = np.random.default_rng(7)
+    hi = 2 ** 31 - 1 if vdtype == torch.int32 else 2 ** 62
+    vl = torch.from_numpy(rng.integers(-hi, hi, size=int(ll.sum()))).to(vdtype)
+    vr = torch.from_numpy(rng.integers(-hi, hi, size=int(lr.sum()))).to(vdtype)
+    got = _jt().concat_1d_jagged_jagged(_dev(ll), vl.to(DEV), _dev(lr), vr.to(DEV))
+    ref = O.concat_1d_jagged_jagged(ll, vl.numpy(), lr, vr.numpy())
+    assert got.dtype == vdtype
+    assert np.array_equal(got.cpu().numpy(), ref)
+
+
+def test_1d_helpers_refuse_2_byte_values():
+    vals = torch.tensor([1, 2, 3, 4, 5, 6], dtype=torch.int16, device=DEV)
+    off = torch.tensor([0, 2, 2, 6], device=DEV)
+    with pytest.raises(RuntimeError, match="expand_1d_jagged_to_dense: elem_bytes must be 4 or 8"):
+        _jt().expand_1d_jagged_to_dense(vals, off, 3)
+    lens = torch.tensor([2, 0, 1], device=DEV)
+    with pytest.raises(RuntimeError, match="concat_1d_jagged_jagged: elem_bytes must be 4 or 8"):
+        _jt().concat_1d_jagged_jagged(lens, vals[:3], lens, vals[3:])
+
+
 def test_large_rows_no_int32_overflow():
     """> 2^31 bytes of payload: row offsets are computed in 64 bits (cf. *_large_tensor tests)."""
     B, D = 4, 1024
