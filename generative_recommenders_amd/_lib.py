@@ -116,6 +116,8 @@ SIGNATURES = {
     "hstu_layer_norm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _int, _vp]),
     "hstu_swish_layer_norm_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _int, _vp]),
     "hstu_swish_layer_norm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _int, _vp]),
+    "hstu_rms_norm_fwd": (_int, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _int, _vp]),
+    "hstu_rms_norm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _int, _vp]),
     "hstu_norm_bwd_workspace_bytes": (C.c_size_t, [_i64, _i32]),
     "hstu_norm_mul_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _int, _int, _int, _vp]),
     "hstu_norm_mul_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _int, _int, _int, _vp]),

@@ -1,7 +1,7 @@
 """Backend enum, module base class and synthetic length generators.
 
 Mirrors the parts of generative_recommenders/common.py that callers of the op layer
-touch: ``HammerKernel`` (:102-107), ``HammerModule`` (:110-170),
+touch: ``HammerKernel`` (:102-107), ``HammerModule`` (:110-170), ``fx_infer_max_len`` (:303-314),
 ``generate_sparse_seq_len`` (:173-201), ``apply_sampling`` (:204-216).  This package has
 ONE backend (the HIP library); the enum keeps the reference's members so existing call
 sites type-check, and adds ``HIP``.  Whatever member is passed, the HIP kernels run --
@@ -70,6 +70,11 @@ class HammerModule(torch.nn.Module, abc.ABC):
     @property
     def is_train(self) -> bool:
         return (not self._is_inference) and self.training
+
+
+def fx_infer_max_len(lengths: torch.Tensor) -> int:
+    """the largest length as a host integer (common.py:303-314; one device sync, as in the reference)"""
+    return int(lengths.max().item())
 
 
 def generate_sparse_seq_len(size: int, max_seq_len: int, sparsity: float, device: torch.device) -> torch.Tensor:

@@ -69,6 +69,13 @@ inline RowClass ln_bwd_class(int dim, int elem_bytes, const void* dy, const void
                              const void* dres, const void* dx) {
   return decide(Facts(dim, elem_bytes).ptr(dy).ptr(x).ptr(w).ptr(b).ptr(dres).ptr(dx));
 }
+// RMS norm: layer norm's classes without the bias (and without a fused residual)
+inline RowClass rms_fwd_class(int dim, int elem_bytes, const void* x, const void* w, const void* y) {
+  return decide(Facts(dim, elem_bytes).ptr(x).ptr(w).ptr(y));
+}
+inline RowClass rms_bwd_class(int dim, int elem_bytes, const void* dy, const void* x, const void* w, const void* dx) {
+  return decide(Facts(dim, elem_bytes).ptr(dy).ptr(x).ptr(w).ptr(dx));
+}
 inline RowClass nm_fwd_class(int heads, int head_dim, int elem_bytes, bool group_norm, const void* attn, const void* u,
                              int64_t u_stride, const void* w, const void* b, const void* y) {
   Facts f(heads * head_dim, elem_bytes);

@@ -301,6 +301,98 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* parti
   }
 }
 
+// ------------------------------------------------------------------ RMS norm
+// y = x rstd w, rstd = 1 / sqrt(mean_j x_j^2 + eps) (RMSNorm, ops/layer_norm.py:139-158; Triton:
+// ops/triton/triton_layer_norm.py:525-749): layer norm's pass without the mean and the bias -- one sum per row instead of
+// two dependent ones, one parameter piece per column instead of two.  Lanes past the row hold zeros, which add nothing.
+template <typename T, int VEC, int MC = max_chunks<VEC>()>
+__global__ __launch_bounds__(kNormThreads) void rms_norm_fwd_kernel(const T* x, const T* w, T* y, float* rstd_out,
+                                                                    int64_t rows, int dim, float eps) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nch = (dim + 64 * VEC - 1) / (64 * VEC);
+  RowVec<T, VEC> wv[MC];
+#pragma unroll
+  for (int k = 0; k < MC; ++k) {
+    const int c = (k * 64 + lane) * VEC;
+    load_piece<T, VEC>(wv[k].v, w + c, k < nch && c < dim);
+  }
+  for (int64_t row = (int64_t)blockIdx.x * kNormWaves + wave; row < rows; row += (int64_t)gridDim.x * kNormWaves) {
+    RowVec<T, VEC> xv[MC];
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < MC; ++k) {
+      const int c = (k * 64 + lane) * VEC;
+      load_piece<T, VEC>(xv[k].v, x + row * dim + c, k < nch && c < dim);
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) q += xv[k].v[i] * xv[k].v[i];
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / dim + eps);
+#pragma unroll
+    for (int k = 0; k < MC; ++k) {
+      const int c = (k * 64 + lane) * VEC;
+      if (k < nch && c < dim) {
+        RowVec<T, VEC> o;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) o.v[i] = xv[k].v[i] * rstd * wv[k].v[i];
+        store_vec<T, VEC>(o, y + row * dim + c);
+      }
+    }
+    if (lane == 0 && rstd_out) rstd_out[row] = rstd;
+  }
+}
+
+// dx = (w dy - xhat mean_j(xhat w dy)) rstd, xhat = x rstd; dweight = sum_r dy xhat per lane, then block_reduce_cols ->
+// columns [0, dim) of this workgroup's partial row (the bias half of the row stays unused) -> reduce_partials_kernel.
+// (The reference adds its per-program partials under a spin lock, in the order the programs arrive.)
+template <typename T, int VEC, int MC = max_chunks<VEC>()>
+__global__ __launch_bounds__(kNormThreads) void rms_norm_bwd_kernel(const T* dy, const T* x, const T* w, const float* rstd_in,
+                                                                    T* dx, float* partial, int64_t rows, int dim) {
+  extern __shared__ float lds[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nch = (dim + 64 * VEC - 1) / (64 * VEC);
+  RowVec<T, VEC> wv[MC];
+  float dw[MC][VEC];
+#pragma unroll
+  for (int k = 0; k < MC; ++k) {
+    const int c = (k * 64 + lane) * VEC;
+    load_piece<T, VEC>(wv[k].v, w + c, k < nch && c < dim);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) dw[k][i] = 0.f;
+  }
+  for (int64_t row = (int64_t)blockIdx.x * kNormWaves + wave; row < rows; row += (int64_t)gridDim.x * kNormWaves) {
+    const float rstd = rstd_in[row];
+    RowVec<T, VEC> xh[MC], g[MC];
+    float s1 = 0.f;
+#pragma unroll
+    for (int k = 0; k < MC; ++k) {
+      const int c = (k * 64 + lane) * VEC;
+      const bool ok = k < nch && c < dim;
+      RowVec<T, VEC> dyv;
+      load_piece<T, VEC>(xh[k].v, x + row * dim + c, ok);
+      load_piece<T, VEC>(dyv.v, dy + row * dim + c, ok);
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) {
+        xh[k].v[i] *= rstd;                         // (padding lanes: x = dy = w = 0)
+        g[k].v[i] = dyv.v[i] * wv[k].v[i];
+        s1 += g[k].v[i] * xh[k].v[i];
+        dw[k][i] += dyv.v[i] * xh[k].v[i];
+      }
+    }
+    const float c1 = wave_sum(s1) / dim;
+#pragma unroll
+    for (int k = 0; k < MC; ++k) {
+      const int c = (k * 64 + lane) * VEC;
+      if (k < nch && c < dim) {
+        RowVec<T, VEC> o;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) o.v[i] = rstd * (g[k].v[i] - xh[k].v[i] * c1);
+        store_vec<T, VEC>(o, dx + row * dim + c);
+      }
+    }
+  }
+  block_reduce_cols<VEC, MC>(dw, lds, partial + (int64_t)blockIdx.x * 2 * dim, dim, nch);
+}
+
 // ------------------------------------------------------------------ y = u * Norm(attn) [, concat]
 // LN: statistics over the whole row, weight/bias per column.
 // GN: statistics per head (head_dim columns), weight/bias per head.
@@ -817,6 +909,38 @@ static int ln_bwd(const RowClass& cls, const void* dy, const void* x, const void
   if (int e = check_launch(who)) return e;
   hipLaunchKernelGGL(reduce_partials_kernel, dim3(2 * dim), dim3(256), 0, st, partial, nb, dim, dweight, dbias);
   return check_launch(who);
+}
+
+template <typename T>
+static int rms_fwd(const RowClass& cls, const void* x, const void* w, void* y, float* rstd, int64_t rows, int dim, float eps,
+                   hipStream_t st) {
+  constexpr int VV = sizeof(T) == 2 ? 8 : 4;
+  int nb;
+#define RMS_ARGS (const T*)x, (const T*)w, (T*)y, rstd, rows, dim, eps
+  if (cls.vec == 1) ROW_LAUNCH(nb, 0, (rms_norm_fwd_kernel<T, 1, max_chunks<1>()>), RMS_ARGS);
+  else if (cls.one_chunk) ROW_LAUNCH(nb, 0, (rms_norm_fwd_kernel<T, VV, 1>), RMS_ARGS);
+  else ROW_LAUNCH(nb, 0, (rms_norm_fwd_kernel<T, VV, max_chunks<VV>()>), RMS_ARGS);
+#undef RMS_ARGS
+  return check_launch("rms_norm_fwd");
+}
+
+template <typename T>
+static int rms_bwd(const RowClass& cls, const void* dy, const void* x, const void* w, const float* rstd, void* dx,
+                   float* dweight, float* partial, int64_t rows, int dim, hipStream_t st) {
+  const int v = cls.vec;
+  constexpr int VV = sizeof(T) == 2 ? 8 : 4;
+  const int nch = (dim + 64 * v - 1) / (64 * v);
+  const size_t lds = (size_t)kNormWaves * nch * 64 * v * sizeof(float);
+  int nb;
+#define RMS_ARGS (const T*)dy, (const T*)x, (const T*)w, rstd, (T*)dx, partial, rows, dim
+  if (v == 1) ROW_LAUNCH(nb, lds, (rms_norm_bwd_kernel<T, 1, max_chunks<1>()>), RMS_ARGS);
+  else if (cls.one_chunk) ROW_LAUNCH(nb, lds, (rms_norm_bwd_kernel<T, VV, 1>), RMS_ARGS);
+  else ROW_LAUNCH(nb, lds, (rms_norm_bwd_kernel<T, VV, max_chunks<VV>()>), RMS_ARGS);
+#undef RMS_ARGS
+  if (int e = check_launch("rms_norm_bwd")) return e;
+  // the weight half of the partial rows only: `dim` columns of the 2 * dim wide matrix, no bias output
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3(dim), dim3(256), 0, st, partial, nb, dim, dweight, (float*)nullptr);
+  return check_launch("rms_norm_bwd(reduce)");
 }
 
 template <typename T>

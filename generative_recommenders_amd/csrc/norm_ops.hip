@@ -7,7 +7,7 @@
 // LDS and written as one fp32 partial per workgroup; a second small kernel sums the
 // partials.  All math is fp32, outputs are cast to the I/O dtype, like the reference:
 //   ops/pytorch/pt_layer_norm.py:24-38, ops/pytorch/pt_hstu_linear.py:23-65;
-// kernels replaced: ops/triton/triton_layer_norm.py:77-309,
+// kernels replaced: ops/triton/triton_layer_norm.py:77-309, :525-749 (RMS norm),
 // ops/triton/triton_hstu_linear.py:48-337 (LN * u), :570-1036 (GroupNorm * u).
 // The pieces and the wave sum are row_pass.cuh's, the grid rule capi_internal.h's (resident_row_blocks): shared with the
 // later row-pass ops (multitask_ops.hip, time_ln_ops.hip, loss_ops.hip).
@@ -128,6 +128,37 @@ int hstu_swish_layer_norm_bwd(const void* dy, const void* x, const void* weight,
   DISPATCH_DTYPE(dtype, NW(k, ln_bwd<bf16_t, true>(k, dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, nullptr, st, bias)),
                  NW(k, ln_bwd<f16_t, true>(k, dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, nullptr, st, bias)),
                  NW(k, ln_bwd<float, true>(k, dy, x, weight, mean, rstd, dx, dweight, dbias, partial_ws, rows, dim, nullptr, st, bias)));
+}
+
+// y = x rstd weight, rstd = 1 / sqrt(mean(x^2) + eps): RMSNorm (rms kernels of norm_kernels.inc)
+int hstu_rms_norm_fwd(const void* x, const void* weight, void* y, float* rstd, int64_t rows, int32_t dim, float eps, int dtype,
+                      void* stream) {
+  if (dim <= 0) return set_error(HSTU_EINVAL, "rms_norm_fwd: dim must be positive");
+  if (rows == 0) return HSTU_OK;
+  if (!x || !weight || !y) return set_error(HSTU_EINVAL, "rms_norm_fwd: NULL tensor");
+  hipStream_t st = (hipStream_t)stream;
+  const RowClass k = norm_dispatch::rms_fwd_class(dim, dtype_bytes(dtype), x, weight, y);
+  if (int e = accept_row(k, dim, "rms_norm_fwd")) return e;
+  DISPATCH_DTYPE(dtype, NW(k, rms_fwd<bf16_t>(k, x, weight, y, rstd, rows, dim, eps, st)),
+                 NW(k, rms_fwd<f16_t>(k, x, weight, y, rstd, rows, dim, eps, st)),
+                 NW(k, rms_fwd<float>(k, x, weight, y, rstd, rows, dim, eps, st)));
+}
+
+int hstu_rms_norm_bwd(const void* dy, const void* x, const void* weight, const float* rstd, void* dx, float* dweight,
+                      float* partial_ws, int64_t rows, int32_t dim, int dtype, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!dweight) return set_error(HSTU_EINVAL, "rms_norm_bwd: dweight is required");
+  if (dim <= 0) return set_error(HSTU_EINVAL, "rms_norm_bwd: dim must be positive");
+  if (rows == 0) {
+    (void)hipMemsetAsync(dweight, 0, dim * sizeof(float), st);
+    return HSTU_OK;
+  }
+  if (!dy || !x || !weight || !rstd || !dx || !partial_ws) return set_error(HSTU_EINVAL, "rms_norm_bwd: NULL tensor");
+  const RowClass k = norm_dispatch::rms_bwd_class(dim, dtype_bytes(dtype), dy, x, weight, dx);
+  if (int e = accept_row(k, dim, "rms_norm_bwd")) return e;
+  DISPATCH_DTYPE(dtype, NW(k, rms_bwd<bf16_t>(k, dy, x, weight, rstd, dx, dweight, partial_ws, rows, dim, st)),
+                 NW(k, rms_bwd<f16_t>(k, dy, x, weight, rstd, dx, dweight, partial_ws, rows, dim, st)),
+                 NW(k, rms_bwd<float>(k, dy, x, weight, rstd, dx, dweight, partial_ws, rows, dim, st)));
 }
 
 static int drop_ratio_ok(float r, const char* who) {

@@ -254,6 +254,29 @@ def _cast(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     return t if t.dtype == dtype else t.detach().to(dtype)
 
 
+class _EmptyRowsFunction(torch.autograd.Function):
+    """A layer stage on a batch of ZERO rows (every user empty: what SDSTU hands its wrapped STU when it skips it): outputs of
+    zero rows, and nothing is launched -- no kernel, no GEMM, no parameter cast.  (The row kernels and hipBLASLt are not asked
+    what they make of an empty operand, and ``view(-1, heads, dim)`` of zero elements is ambiguous to torch.)  Backward hands
+    empty gradients to the activations and none to the parameters: a sum over no rows."""
+
+    @staticmethod
+    def forward(ctx, out_shapes, num_activations, *inputs):
+        like = inputs[0]
+        ctx.acts = [(t.shape, t.dtype, t.device) for t in inputs[:num_activations]]
+        ctx.num_params = len(inputs) - num_activations
+        return tuple(like.new_empty(s) for s in out_shapes)
+
+    @staticmethod
+    def backward(ctx, *douts):
+        return (None, None) + tuple(torch.empty(s, dtype=d, device=dev) for s, d, dev in ctx.acts) + (None,) * ctx.num_params
+
+
+def _empty_rows(out_shapes, activations, params):
+    """outputs of the shapes ``out_shapes`` (all with zero rows) in the first activation's dtype, as one autograd node"""
+    return _EmptyRowsFunction.apply(tuple(out_shapes), len(activations), *activations, *params)
+
+
 class _NormMulFunction(torch.autograd.Function):
     """y = dropout(u * Norm(attn)) (optionally [u, attn, y]) as a node of its own, without the GEMM: the research layer's
     output stage (its projection is an nn.Linear) and the tests' handle on the row kernels.  Dropout is fused exactly as in
@@ -353,6 +376,8 @@ def hstu_compute_output(
     del kernel
     p_drop = float(dropout_ratio) if training else 0.0
     torch._assert(0.0 <= p_drop < 1.0, "dropout_ratio must be in [0, 1)")
+    if x.shape[0] == 0:
+        return _empty_rows([(0, x.shape[1])], (x, attn, u), (norm_weight, norm_bias, output_weight))[0]
     seed = draw_dropout_seed() if p_drop > 0.0 else 0
     return _ComputeOutputFunction.apply(attn, u, x, norm_weight, norm_bias, output_weight, norm_eps, num_heads,
                                         linear_dim, concat_ux, group_norm, recompute_y_in_backward, p_drop, seed,
@@ -575,6 +600,9 @@ def hstu_fused_layer(
     torch._assert(hstu_fused_layer_applicable(x, attn_dim, hidden_dim), "head dims must be 16-byte multiples")
     p_drop = float(dropout_ratio) if training else 0.0
     torch._assert(0.0 <= p_drop < 1.0, "dropout_ratio must be in [0, 1)")
+    if x.shape[0] == 0:
+        return _empty_rows([(0, x.shape[1])], (x,), (input_norm_weight, input_norm_bias, uvqk_weight, uvqk_bias, output_norm_weight,
+                                                     output_norm_bias, output_weight))[0]
     seed = draw_dropout_seed() if p_drop > 0.0 else 0
     order = _launch.length_order(_launch._idx(seq_offsets)) if sort_by_length and seq_offsets.numel() > 2 else None
     return _STULayerFunction.apply(
@@ -617,6 +645,11 @@ def hstu_preprocess_and_attention(
     torch._assert(causal is True, "only causal attention is supported.")
     es = x.element_size()
     fusable = (attn_dim * es) % 16 == 0 and (hidden_dim * es) % 16 == 0
+    if x.shape[0] == 0:
+        hv, with_kv = hidden_dim * num_heads, prefill or not fusable
+        shapes = [(0, hv), (0, hv)] + ([(0, num_heads, attn_dim), (0, num_heads, hidden_dim)] if with_kv else [])
+        outs = _empty_rows(shapes, (x,), (norm_weight, norm_bias, uvqk_weight, uvqk_bias))
+        return (outs[0], outs[1], outs[2], outs[3]) if with_kv else (outs[0], outs[1], None, None)
     if not prefill and fusable:
         u, attn_output = _PreprocessAndAttentionFunction.apply(
             x, norm_weight, norm_bias, uvqk_weight, uvqk_bias, seq_offsets, num_targets, norm_eps, num_heads,

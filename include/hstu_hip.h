@@ -275,6 +275,18 @@ int hstu_swish_layer_norm_fwd(const void* x, const void* weight, const void* bia
 int hstu_swish_layer_norm_bwd(const void* dy, const void* x, const void* weight, const void* bias, const float* mean,
                               const float* rstd, void* dx, float* dweight, float* dbias, float* partial_ws, int64_t rows,
                               int32_t dim, int dtype, void* stream);
+/* RMS norm (additive to ABI v13): y = x rstd weight with rstd = 1 / sqrt(mean_j(x_j^2) + eps) -- RMSNorm
+ * (ops/layer_norm.py:139-158; Triton: ops/triton/triton_layer_norm.py:525-749, whose semantics these follow: fp32 math,
+ * one rounding at the store, y in x's dtype).  Same contract as hstu_layer_norm_fwd / _bwd without the mean and the bias:
+ * weight (dim) in `dtype`, rstd (fp32, per row) is an output of the forward (may be NULL) and an input of the backward,
+ *   dx = (weight dy - xhat mean_j(xhat weight dy)) rstd,  dweight_j = sum_r dy_rj xhat_rj  (fp32),  xhat = x rstd;
+ * partial_ws of hstu_norm_bwd_workspace_bytes(rows, dim) bytes; dweight is summed in a fixed order (no atomics, no locks:
+ * bit-identical run to run); rows == 0 launches nothing and zeroes dweight.  dim <= 4096 (rows read in 16-byte pieces) /
+ * 2048 (element by element), as hstu_layer_norm_fwd. */
+int hstu_rms_norm_fwd(const void* x, const void* weight, void* y, float* rstd, int64_t rows, int32_t dim, float eps,
+                      int dtype, void* stream);
+int hstu_rms_norm_bwd(const void* dy, const void* x, const void* weight, const float* rstd, void* dx, float* dweight,
+                      float* partial_ws, int64_t rows, int32_t dim, int dtype, void* stream);
 /* ABI v11: y = x . W^T (+ bias) for a contraction length of 512 -- the same kernel without the LayerNorm (rows of x in
  * registers, W streamed through LDS).  Used for d y = d out . W_out^T in the output stage's backward, where k is the
  * embedding dim and the (n, k) K-contiguous operand is the reference's (3 H d, D) `_output_weight` as stored
