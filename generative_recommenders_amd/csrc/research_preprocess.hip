@@ -36,6 +36,18 @@ namespace {
 HSTU_DEV float mul_rn(float a, float b) { return a * b; }
 HSTU_DEV float add_rn(float a, float b) { return a + b; }
 
+// the fp32 value rounded to the stored dtype.  In the one-element fp16 kernels the value is pinned in its register first:
+// there the compiler folds the product in front of the store into the conversion (one v_fma_mixlo_f16 with a +0 addend),
+// which rounds once where fl16(fl32(.)) is promised and turns the -0 of a masked row into +0.  (The pin is an asm
+// statement, which rules out a partial unroll: those kernels ask for none.)
+template <typename T, int V> constexpr bool kPinned = V == 1 && __is_same(T, f16_t);
+template <typename T, int V> constexpr int kUserUnroll = kPinned<T, V> ? 1 : 2;      // of the loop over a slab's users
+template <typename T, int V>
+HSTU_DEV T narrow(float x) {
+  if constexpr (kPinned<T, V>) asm("" : "+v"(x));
+  return (T)x;
+}
+
 constexpr int kThreads = 256;
 constexpr int kMaxUnitBlocks = 1024;      // grid.x cap; the pieces beyond are grid-strided
 constexpr int kFwdBlocks = 2048;          // 256 CUs x 8 resident workgroups
@@ -110,7 +122,7 @@ __global__ __launch_bounds__(kThreads) void input_preprocess_fwd_kernel(
   for (int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x; j < units; j += (int64_t)gridDim.x * kThreads) {
     const Piece p = piece_of<LAYOUT, V>(j, upr, a);
     const Pack<TO, V> pp = load_pack<TO, V>(pos + (int64_t)p.np * a.Do + p.c);
-#pragma unroll 2
+#pragma unroll kUserUnroll<TO, V>
     for (int b = b0; b < b1; ++b) {
       const int64_t row = (int64_t)b * a.N + p.n;
       const int64_t orow = (int64_t)b * a.Nout + p.np;
@@ -132,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void input_preprocess_fwd_kernel(
       for (int i = 0; i < V; ++i) {
         float v = add_rn(mul_rn(x[i], a.s), (float)pp.e[i]);
         if (a.thr) v = ((kb >> i) & 1u) ? mul_rn(v, a.scale) : 0.f;
-        o.e[i] = (TO)mul_rn(v, m);          // the product, not a select: the reference's masked rows keep their sign
+        o.e[i] = narrow<TO, V>(mul_rn(v, m));  // the product, not a select: the reference's masked rows keep their sign
       }
       store_pack<TO, V>(out + e0, o);
       if (p.c == 0) valid[orow] = m;
@@ -153,7 +165,7 @@ __global__ __launch_bounds__(kThreads) void input_preprocess_bwd_kernel(
     Pack<float, V> acc;
 #pragma unroll
     for (int i = 0; i < V; ++i) acc.e[i] = 0.f;
-#pragma unroll 2
+#pragma unroll kUserUnroll<TE, V>
     for (int b = b0; b < b1; ++b) {
       const int64_t row = (int64_t)b * a.N + p.n;
       const int64_t e0 = ((int64_t)b * a.Nout + p.np) * a.Do + p.c;
@@ -166,7 +178,7 @@ __global__ __launch_bounds__(kThreads) void input_preprocess_bwd_kernel(
         float h = mul_rn((float)gq.e[i], m);
         if (a.thr) h = ((kb >> i) & 1u) ? mul_rn(h, a.scale) : 0.f;
         acc.e[i] = add_rn(acc.e[i], h);
-        o.e[i] = (TE)mul_rn(h, a.s);
+        o.e[i] = narrow<TE, V>(mul_rn(h, a.s));
       }
       if (d_emb && !p.rating) store_pack<TE, V>(d_emb + row * a.Di + p.cs, o);
     }

@@ -151,6 +151,100 @@ def combine_bwd(d_out, lengths, num_targets, C, mode, has_action):
     return d_content, d_action, d_ctx
 
 
+# ------------------------------------------------------------------------------------------------------ index maps
+# The same formulas as whole-array index maps, for batches of 10^5 rows (tests/test_input_stage_classes_gpu.py);
+# tests/test_preprocessor_host.py shows them equal to the per-row loops above.
+def action_row_map(uih_offsets, target_offsets):
+    """per output row: (the UIH row it encodes, or -1 for a target row)"""
+    uo, to = np.asarray(uih_offsets, dtype=np.int64), np.asarray(target_offsets, dtype=np.int64)
+    U, Tn = np.diff(uo), np.diff(to)
+    b = np.repeat(np.arange(len(U)), U + Tn)
+    i = np.arange(int((U + Tn).sum())) - (uo + to)[b]
+    return np.where(i < U[b], uo[b] + i, -1)
+
+
+def _action_bits(actions, watchtimes, weights, thresholds):
+    """(rows, T) bool: the bit test of every UIH row against every combined weight"""
+    a = effective_actions(actions, watchtimes, thresholds)
+    return (a[:, None] & np.asarray([int(w) for w in weights], dtype=np.int64)[None, :]) > 0
+
+
+def action_encode_mapped(actions, watchtimes, uih_offsets, target_offsets, table, target_table, weights, thresholds):
+    table, target_table = np.asarray(table), np.asarray(target_table).reshape(-1)
+    T, da = table.shape
+    src = action_row_map(uih_offsets, target_offsets)
+    out = np.empty((src.size, T * da), dtype=table.dtype)
+    out[src < 0] = target_table
+    s = src[src >= 0]
+    on = np.repeat(_action_bits(actions, watchtimes, weights, thresholds)[s], da, axis=1)
+    out[src >= 0] = np.where(on, table.reshape(-1)[None, :], signed_zero(table).reshape(-1)[None, :])
+    return out
+
+
+def action_encode_bwd_mapped(d_out, actions, watchtimes, uih_offsets, target_offsets, weights, thresholds, da):
+    d_out = np.asarray(d_out, dtype=np.float64)
+    T = len(weights)
+    src = action_row_map(uih_offsets, target_offsets)
+    assert src.size == d_out.shape[0]
+    g = d_out[src >= 0].reshape(-1, T, da)
+    on = _action_bits(actions, watchtimes, weights, thresholds)[src[src >= 0]].astype(np.float64)
+    tg = d_out[src < 0]
+    return dict(d_table=np.einsum("rt,rtd->td", on, g), abs_table=np.einsum("rt,rtd->td", on, np.abs(g)),
+                n_table=np.repeat(on.sum(0)[:, None], da, axis=1), d_target=tg.sum(0), abs_target=np.abs(tg).sum(0),
+                n_target=np.full(T * da, tg.shape[0], dtype=np.float64))
+
+
+def combine_row_map(lengths, num_targets, C, mode):
+    """per output row: (user, contextual index or -1, source row or -1, takes the action row?)"""
+    L, T = np.asarray(lengths, dtype=np.int64), np.asarray(num_targets, dtype=np.int64)
+    n = out_lengths(L, T, C, mode)
+    b = np.repeat(np.arange(len(L)), n)
+    j = np.arange(int(n.sum())) - offsets_of(n)[b]
+    p = j - C
+    if mode == SUM:
+        i, act = p, np.zeros(p.shape, dtype=bool)
+    else:
+        U = (L - T if mode == INTERLEAVE_UIH else L)[b]
+        i, act = np.where(p < 2 * U, p >> 1, p - U), (p < 2 * U) & ((p & 1) == 1)
+    ctx = j < C
+    return b, np.where(ctx, j, -1), np.where(ctx, -1, offsets_of(L)[b] + i), act & ~ctx
+
+
+def combine_mapped(content, action, contextual, timestamps, lengths, num_targets, mode, summed=None):
+    content = np.asarray(content)
+    C = 0 if contextual is None else contextual.shape[1]
+    b, j, src, act = combine_row_map(lengths, num_targets, C, mode)
+    emb = np.empty((b.size, content.shape[1]), dtype=content.dtype)
+    seq = j < 0
+    if C:
+        emb[~seq] = contextual[b[~seq], j[~seq]]
+    first = content if (mode != SUM or action is None) else summed
+    emb[seq] = first[src[seq]]
+    if mode != SUM:
+        emb[act] = action[src[act]]
+    ts = np.where(seq, np.asarray(timestamps, dtype=np.int64)[np.maximum(src, 0)], 0) if b.size else np.zeros(0, dtype=np.int64)
+    return emb, ts.astype(np.int64), out_lengths(lengths, num_targets, C, mode)
+
+
+def combine_bwd_mapped(d_out, lengths, num_targets, C, mode, has_action):
+    d_out = np.asarray(d_out)
+    D, B, total = d_out.shape[1], len(lengths), int(np.sum(lengths))
+    b, j, src, act = combine_row_map(lengths, num_targets, C, mode)
+    seq = j < 0
+    d_content = np.zeros((total, D), dtype=d_out.dtype)
+    d_content[src[seq & ~act]] = d_out[seq & ~act]
+    d_action = None
+    if has_action:
+        d_action = d_content.copy() if mode == SUM else np.zeros((total, D), dtype=d_out.dtype)
+        if mode != SUM:
+            d_action[src[act]] = d_out[act]
+    d_ctx = None
+    if C > 0:
+        d_ctx = np.zeros((B, C, D), dtype=d_out.dtype)
+        d_ctx[b[~seq], j[~seq]] = d_out[~seq]
+    return d_content, d_action, d_ctx
+
+
 def candidates(values, lengths, num_targets, interleave):
     """the last num_targets rows of every user (of the OUTPUT sequence), every second one when the targets are interleaved"""
     off = offsets_of(lengths)

@@ -194,6 +194,43 @@ def test_contextual_preprocessor_fixture_layout():
     assert np.array_equal(again, emb) and np.array_equal(ts, c["f32:out:seq_timestamps"])
 
 
+def test_index_map_restatement_equals_the_per_row_loops():
+    """the whole-array paths of preprocessor_ref.py (for the large batches of test_input_stage_classes_gpu.py) against its
+    per-row loops, on the 17 users of test_preprocessor_gpu.py: moves bit for bit, the fp64 sums exactly (integer terms)"""
+    lengths = np.array([7, 0, 4, 3, 9, 40, 12, 1, 5, 2, 31, 8, 16, 6, 23, 11, 3])
+    targets = np.array([2, 0, 0, 3, 1, 7, 0, 0, 5, 1, 4, 8, 3, 2, 9, 1, 1])
+    rng = np.random.default_rng(17)
+    total, uih = int(lengths.sum()), lengths - targets
+    uo, to = R.offsets_of(uih), R.offsets_of(targets)
+    for weights, thresholds, da in (([2, 1, 4], [(10, 1), (50, 4)], 5), ([1 << 62, 3, (1 << 40) | 8, 16], [(30, 16)], 8)):
+        T = len(weights)
+        actions = rng.integers(0, 2**63 - 1, int(uih.sum())) if max(weights) > 2**32 else rng.integers(0, 16, int(uih.sum()))
+        watch = rng.integers(0, 100, int(uih.sum()))
+        table = rng.integers(0, 2**16, (T, da)).astype(np.uint16)
+        target = rng.integers(0, 2**16, T * da).astype(np.uint16)
+        args = (actions, watch, uo, to, table, target, weights, thresholds)
+        assert np.array_equal(R.action_encode_mapped(*args), R.action_encode(*args))
+        d_out = rng.integers(-8, 9, (total, T * da)).astype(np.float64)
+        a, b = (f(d_out, actions, watch, uo, to, weights, thresholds, da) for f in (R.action_encode_bwd_mapped, R.action_encode_bwd))
+        assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    content, action = (rng.integers(0, 2**16, (total, 6)).astype(np.uint16) for _ in range(2))
+    summed = rng.integers(0, 2**16, (total, 6)).astype(np.uint16)
+    ts = rng.integers(1, 10**9, total)
+    for mode in (R.SUM, R.INTERLEAVE_ALL, R.INTERLEAVE_UIH):
+        for C in (0, 3):
+            ctx = rng.integers(0, 2**16, (len(lengths), C, 6)).astype(np.uint16) if C else None
+            for has_action in ((True, False) if mode == R.SUM else (True,)):
+                args = (content, action if has_action else None, ctx, ts, lengths, targets, mode, summed if has_action else None)
+                got, want = R.combine_mapped(*args), R.combine(*args)
+                assert all(np.array_equal(g, w) and g.dtype == w.dtype for g, w in zip(got, want)), (mode, C, has_action)
+                d_out = rng.integers(1, 2**16, want[0].shape).astype(np.uint16)
+                got = R.combine_bwd_mapped(d_out, lengths, targets, C, mode, has_action)
+                want = R.combine_bwd(d_out, lengths, targets, C, mode, has_action)
+                assert all((g is None and w is None) or np.array_equal(g, w) for g, w in zip(got, want)), (mode, C, has_action)
+    b, j, src, act = R.combine_row_map([], [], 3, R.INTERLEAVE_UIH)
+    assert b.size == 0 and R.action_row_map([0], [0]).size == 0
+
+
 def test_restatement_backward_is_the_inverse_of_the_forward():
     """combine_bwd(combine(x)) returns x for every row that the forward copied (and zeros for the dropped action targets)"""
     rng = np.random.default_rng(0)
