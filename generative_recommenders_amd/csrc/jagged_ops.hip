@@ -11,6 +11,7 @@
 #include "hstu_common.cuh"
 #include "capi_internal.h"
 #include "jagged_dispatch.h"
+#include "row_slots.h"
 
 namespace hstu {
 
@@ -56,21 +57,16 @@ __global__ __launch_bounds__(kCopyThreads) void concat_split_kernel(char* left, 
   const int r_begin = blockIdx.y * kRowsPerBlock;
   if (r_begin >= total) return;
   const int np = min(n_prefix, lr);
-  // threads split as (rows in flight) x (lanes per row)
-  const int units = max(row_bytes / V, 1);
-  int tpr = 1;
-  while (tpr < units && tpr < kCopyThreads) tpr <<= 1;       // threads per row (power of two)
-  const int rows_par = kCopyThreads / tpr;
-  const int t_in_row = threadIdx.x % tpr, my_row_slot = threadIdx.x / tpr;
+  const RowSlots s = row_slots(max(row_bytes / V, 1), kCopyThreads);   // (rows in flight) x (lanes per row)
   const int r_end = min(r_begin + kRowsPerBlock, total);
-  for (int r = r_begin + my_row_slot; r < r_end; r += rows_par) {
+  for (int r = r_begin + s.slot; r < r_end; r += s.rows_par) {
     char* side;
     if (r < np) side = right + (orr + r) * (int64_t)row_bytes;
     else if (r < np + ll) side = left + (ol + (r - np)) * (int64_t)row_bytes;
     else side = right + (orr + (r - ll)) * (int64_t)row_bytes;
     char* c = comb + (ol + orr + r) * (int64_t)row_bytes;
-    if (SPLIT) copy_row<V>(side, c, row_bytes, t_in_row, tpr);
-    else copy_row<V>(c, side, row_bytes, t_in_row, tpr);
+    if (SPLIT) copy_row<V>(side, c, row_bytes, s.lane, s.tpr);
+    else copy_row<V>(c, side, row_bytes, s.lane, s.tpr);
   }
 }
 
@@ -84,17 +80,13 @@ __global__ __launch_bounds__(kCopyThreads) void padded_dense_kernel(char* values
   const int r_begin = blockIdx.y * kRowsPerBlock;
   const int limit = TO_DENSE ? max_len : len;
   if (r_begin >= limit) return;
-  const int units = max(row_bytes / V, 1);
-  int tpr = 1;
-  while (tpr < units && tpr < kCopyThreads) tpr <<= 1;
-  const int rows_par = kCopyThreads / tpr;
-  const int t_in_row = threadIdx.x % tpr, my_row_slot = threadIdx.x / tpr;
+  const RowSlots s = row_slots(max(row_bytes / V, 1), kCopyThreads);
   const int r_end = min(r_begin + kRowsPerBlock, limit);
-  for (int r = r_begin + my_row_slot; r < r_end; r += rows_par) {
+  for (int r = r_begin + s.slot; r < r_end; r += s.rows_par) {
     char* d = dense + ((int64_t)b * max_len + r) * row_bytes;
     char* v = values + (off + r) * (int64_t)row_bytes;
-    if (TO_DENSE) copy_row<V>(d, r < len ? v : nullptr, row_bytes, t_in_row, tpr);
-    else copy_row<V>(v, d, row_bytes, t_in_row, tpr);
+    if (TO_DENSE) copy_row<V>(d, r < len ? v : nullptr, row_bytes, s.lane, s.tpr);
+    else copy_row<V>(v, d, row_bytes, s.lane, s.tpr);
   }
 }
 
@@ -107,15 +99,11 @@ __global__ __launch_bounds__(kCopyThreads) void write_tail_kernel(const char* de
   const int64_t end = load_index(offsets, b + 1, is64);
   const int r_begin = blockIdx.y * kRowsPerBlock;
   if (r_begin >= tail) return;
-  const int units = max(row_bytes / V, 1);
-  int tpr = 1;
-  while (tpr < units && tpr < kCopyThreads) tpr <<= 1;
-  const int rows_par = kCopyThreads / tpr;
-  const int t_in_row = threadIdx.x % tpr, my_row_slot = threadIdx.x / tpr;
+  const RowSlots s = row_slots(max(row_bytes / V, 1), kCopyThreads);
   const int r_end = min(r_begin + kRowsPerBlock, tail);
-  for (int r = r_begin + my_row_slot; r < r_end; r += rows_par)
+  for (int r = r_begin + s.slot; r < r_end; r += s.rows_par)
     copy_row<V>(values + (end - tail + r) * (int64_t)row_bytes, dense + ((int64_t)b * tail + r) * row_bytes, row_bytes,
-                t_in_row, tpr);
+                s.lane, s.tpr);
 }
 
 // out[0] = 0, out[i+1] = in[0] + ... + in[i].  One workgroup, chunked wave scan with carry

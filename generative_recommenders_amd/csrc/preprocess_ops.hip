@@ -10,18 +10,19 @@
 //                                       every output row and timestamp once; backward = the inverse gather.
 //
 // Geometry of all four: the grid is the resident workgroups (at most 8 per CU), every workgroup owns ONE contiguous slab of
-// rows, its 256 threads split as (rows in flight) x (lanes per row) as in jagged_ops.hip.  The user of a row is found by
-// one binary search over the offsets per row slot and then advanced linearly along the slab.  Rows are 16-byte pieces when
-// the row bytes and the base pointers allow it (VEC), elements otherwise.
+// rows, its 256 threads split as (rows in flight) x (lanes per row) by row_slots.h.  The user of a row is found by one
+// binary search over the offsets per row slot and then advanced linearly along the slab.  Rows are 16-byte pieces when the
+// row bytes and the base pointers allow it (VEC), elements otherwise.  Everything the host decides -- grids, slab counts,
+// the piece width, the workspace size -- comes from input_stage_dispatch.h, which a CPU test compiles alone.
 #include "hstu_common.cuh"
 #include "capi_internal.h"
+#include "input_stage_dispatch.h"
 
 namespace hstu {
+using namespace input_stage;
 
-constexpr int kPreThreads = 256;
-constexpr int kPreBlocksPerCu = 8;
 constexpr int kActionMaxTypes = HSTU_ACTION_ENCODE_MAX_TYPES;
-constexpr int kActionBwdGroupsMax = 512;
+static_assert(kCombineSum == HSTU_COMBINE_SUM && kCombineInterleaveAll == HSTU_COMBINE_INTERLEAVE_ALL, "input_stage_dispatch.h");
 
 template <typename T> struct Vec16;   // 16 bytes of T
 template <> struct Vec16<bf16_t> { typedef bf16_t type __attribute__((ext_vector_type(8))); static constexpr int N = 8; };
@@ -79,38 +80,6 @@ HSTU_DEV Piece<T, VEC> cast_piece(const float* p, float m) {
   return r;
 }
 
-// threads of a workgroup as (rows in flight) x (lanes per row)
-struct RowSlots {
-  int tpr, rows_par, lane, slot;
-};
-HSTU_DEV RowSlots row_slots(int units) {
-  RowSlots s;
-  s.tpr = 1;
-  while (s.tpr < units && s.tpr < kPreThreads) s.tpr <<= 1;
-  s.rows_par = kPreThreads / s.tpr;
-  s.lane = threadIdx.x % s.tpr;
-  s.slot = threadIdx.x / s.tpr;
-  return s;
-}
-
-// the workgroup's slab [r0, r1) of `rows` rows
-HSTU_DEV void slab_of(int64_t rows, int64_t* r0, int64_t* r1) {
-  const int64_t per = (rows + gridDim.x - 1) / gridDim.x;
-  *r0 = (int64_t)blockIdx.x * per;
-  *r1 = min(*r0 + per, rows);
-}
-
-// the largest b in [0, batch) with off(b) <= r
-template <typename F>
-HSTU_DEV int find_user(F off, int batch, int64_t r) {
-  int lo = 0, hi = batch - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off(mid) <= r) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 // ------------------------------------------------------------------------------------------------ action encode
 struct ActionArgs {
   int64_t weight[kActionMaxTypes];        // the combined action weights: one bit pattern per column block
@@ -139,7 +108,7 @@ __global__ __launch_bounds__(kPreThreads) void action_encode_fwd_kernel(
   constexpr int N = Piece<T, VEC>::N;
   const int width = a.num_types * da;
   const int units = width / N;
-  const RowSlots s = row_slots(units);
+  const RowSlots s = row_slots(units, kPreThreads);
   int64_t r0, r1;
   slab_of(rows, &r0, &r1);
   int64_t r = r0 + s.slot;
@@ -181,7 +150,7 @@ __global__ __launch_bounds__(kPreThreads) void action_encode_bwd_kernel(
   __shared__ float red[kPreThreads][2 * N + 1];
   const int width = a.num_types * da;
   const int units = width / N;
-  const RowSlots s = row_slots(units);
+  const RowSlots s = row_slots(units, kPreThreads);
   const int u = blockIdx.y * s.tpr + s.lane;
   const bool live = u < units;
   const int c = u * N;
@@ -255,32 +224,6 @@ __global__ __launch_bounds__(256) void action_encode_bwd_finish_kernel(const flo
   if (idx < width) d_table[idx] = t; else d_target_table[idx - width] = t;
 }
 
-static int resident_blocks(int64_t rows, int rows_par) {
-  int64_t b = (rows + rows_par - 1) / rows_par;
-  const int64_t cap = (int64_t)cu_count() * kPreBlocksPerCu;
-  if (b > cap) b = cap;
-  return b < 1 ? 1 : (int)b;
-}
-
-static int host_rows_par(int units) {
-  int tpr = 1;
-  while (tpr < units && tpr < kPreThreads) tpr <<= 1;
-  return kPreThreads / tpr;
-}
-
-static int action_bwd_groups(int64_t rows, int units) {
-  // slabs of at least 8 rows per row slot; 2 workgroups per CU keep every CU reading
-  int64_t g = (rows + 8 * host_rows_par(units) - 1) / (8 * host_rows_par(units));
-  const int64_t cap = (int64_t)cu_count() * 2;
-  if (g > cap) g = cap;
-  if (g > kActionBwdGroupsMax) g = kActionBwdGroupsMax;
-  return g < 1 ? 1 : (int)g;
-}
-
-static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
-  return ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d)) & 15) == 0;
-}
-
 static int fill_action_args(ActionArgs* a, const int64_t* weights, int num_types, const int64_t* thresholds,
                             const int64_t* threshold_weights, int num_thresholds, const char* what) {
   if (num_types < 1 || num_types > kActionMaxTypes)
@@ -313,12 +256,9 @@ template <typename T>
 static int action_fwd_t(const int64_t* actions, const int64_t* watchtimes, const void* uo, const void* to, const float* table,
                         const float* target_table, const ActionArgs& a, void* out, int64_t rows, int64_t total_uih, int batch,
                         int da, int is64, hipStream_t st) {
-  const int width = a.num_types * da;
-  constexpr int N = Vec16<T>::N;
-  const bool vec = da % N == 0 && aligned16(table, target_table, out);
-  const int units = vec ? width / N : width;
-  const dim3 grid(resident_blocks(rows, host_rows_par(units)));
-  if (vec)
+  const int piece = action_fwd_piece(da, sizeof(T), table, target_table, out);
+  const dim3 grid(resident_blocks(rows, rows_in_flight(a.num_types * da / piece, kPreThreads), cu_count()));
+  if (piece > 1)
     hipLaunchKernelGGL((action_encode_fwd_kernel<T, true>), grid, dim3(kPreThreads), 0, st, actions, watchtimes, uo, to, table,
                        target_table, a, (T*)out, rows, total_uih, batch, da, is64);
   else
@@ -332,19 +272,18 @@ static int action_bwd_t(const void* d_out, const int64_t* actions, const int64_t
                         const ActionArgs& a, float* d_table, float* d_target, float* partial, int64_t rows, int64_t total_uih,
                         int batch, int da, int is64, hipStream_t st) {
   const int width = a.num_types * da;
-  constexpr int N = Vec16<T>::N;
-  const bool vec = da % N == 0 && aligned16(d_out, partial);
-  const int units = vec ? width / N : width;
-  const int groups = action_bwd_groups(rows, units);
-  const dim3 grid(groups, (units + kPreThreads - 1) / kPreThreads);
-  if (vec)
+  const int piece = action_bwd_piece(da, sizeof(T), d_out, partial);
+  const int units = width / piece;
+  const int groups = action_bwd_groups(rows, units, cu_count());
+  const dim3 grid(groups, action_bwd_grid_y(units));
+  if (piece > 1)
     hipLaunchKernelGGL((action_encode_bwd_kernel<T, true>), grid, dim3(kPreThreads), 0, st, (const T*)d_out, actions, watchtimes,
                        uo, to, a, partial, rows, total_uih, batch, da, is64);
   else
     hipLaunchKernelGGL((action_encode_bwd_kernel<T, false>), grid, dim3(kPreThreads), 0, st, (const T*)d_out, actions, watchtimes,
                        uo, to, a, partial, rows, total_uih, batch, da, is64);
   if (int e = check_launch("hstu_action_encode_bwd")) return e;
-  hipLaunchKernelGGL(action_encode_bwd_finish_kernel, dim3((2 * width + 255) / 256), dim3(256), 0, st, partial, groups, width,
+  hipLaunchKernelGGL(action_encode_bwd_finish_kernel, dim3(action_bwd_finish_blocks(width)), dim3(256), 0, st, partial, groups, width,
                      d_table, d_target);
   return check_launch("hstu_action_encode_bwd(finish)");
 }
@@ -372,7 +311,7 @@ __global__ __launch_bounds__(kPreThreads) void combine_fwd_kernel(
     int batch, int C, int D, int mode, int is64) {
   constexpr int N = Piece<T, VEC>::N;
   const int units = D / N;
-  const RowSlots s = row_slots(units);
+  const RowSlots s = row_slots(units, kPreThreads);
   int64_t r0, r1;
   slab_of(out_rows, &r0, &r1);
   int64_t r = r0 + s.slot;
@@ -432,7 +371,7 @@ __global__ __launch_bounds__(kPreThreads) void combine_bwd_kernel(
     int64_t total_rows, int64_t out_rows, int batch, int C, int D, int mode, int is64) {
   constexpr int N = Piece<T, VEC>::N;
   const int units = D / N;
-  const RowSlots s = row_slots(units);
+  const RowSlots s = row_slots(units, kPreThreads);
   const int64_t ctx_rows = d_contextual ? (int64_t)batch * C : 0;
   int64_t r0, r1;
   slab_of(total_rows + ctx_rows, &r0, &r1);
@@ -478,15 +417,13 @@ template <typename T>
 static int combine_fwd_t(const void* content, const void* action, const void* contextual, const int64_t* ts, const void* seq_off,
                          const void* nt, const void* out_off, void* out, int64_t* out_ts, int64_t total_rows, int64_t out_rows,
                          int batch, int C, int D, int mode, int is64, hipStream_t st) {
-  constexpr int N = Vec16<T>::N;
-  const bool vec = D % N == 0 && aligned16(content, action, contextual, out);
-  const int units = vec ? D / N : D;
-  const dim3 grid(resident_blocks(out_rows, host_rows_par(units)));
+  const int piece = combine_fwd_piece(D, sizeof(T), content, action, contextual, out);
+  const dim3 grid(resident_blocks(out_rows, rows_in_flight(D / piece, kPreThreads), cu_count()));
 #define LAUNCH(V)                                                                                                             \
   hipLaunchKernelGGL((combine_fwd_kernel<T, V>), grid, dim3(kPreThreads), 0, st, (const T*)content, (const T*)action,           \
                      (const T*)contextual, ts, seq_off, nt, out_off, (T*)out, out_ts, total_rows, out_rows, batch, C, D, mode,  \
                      is64)
-  if (vec) LAUNCH(true); else LAUNCH(false);
+  if (piece > 1) LAUNCH(true); else LAUNCH(false);
 #undef LAUNCH
   return check_launch("hstu_combine_embeddings_fwd");
 }
@@ -495,24 +432,15 @@ template <typename T>
 static int combine_bwd_t(const void* d_out, const void* seq_off, const void* nt, const void* out_off, void* d_content,
                          void* d_action, void* d_contextual, int64_t total_rows, int64_t out_rows, int batch, int C, int D,
                          int mode, int is64, hipStream_t st) {
-  constexpr int N = Vec16<T>::N;
-  const bool vec = D % N == 0 && aligned16(d_out, d_content, d_action, d_contextual);
-  const int units = vec ? D / N : D;
-  const int64_t rows = total_rows + (d_contextual ? (int64_t)batch * C : 0);
-  const dim3 grid(resident_blocks(rows, host_rows_par(units)));
+  const int piece = combine_bwd_piece(D, sizeof(T), d_out, d_content, d_action, d_contextual);
+  const int64_t rows = combine_bwd_rows(total_rows, batch, C, d_contextual != nullptr);
+  const dim3 grid(resident_blocks(rows, rows_in_flight(D / piece, kPreThreads), cu_count()));
 #define LAUNCH(V)                                                                                                            \
   hipLaunchKernelGGL((combine_bwd_kernel<T, V>), grid, dim3(kPreThreads), 0, st, (const T*)d_out, seq_off, nt, out_off,        \
                      (T*)d_content, (T*)d_action, (T*)d_contextual, total_rows, out_rows, batch, C, D, mode, is64)
-  if (vec) LAUNCH(true); else LAUNCH(false);
+  if (piece > 1) LAUNCH(true); else LAUNCH(false);
 #undef LAUNCH
   return check_launch("hstu_combine_embeddings_bwd");
-}
-
-static int64_t combine_out_rows(int mode, int64_t total_uih, int64_t total_targets, int batch, int C) {
-  const int64_t ctx = (int64_t)batch * C;
-  if (mode == HSTU_COMBINE_SUM) return ctx + total_uih + total_targets;
-  if (mode == HSTU_COMBINE_INTERLEAVE_ALL) return ctx + 2 * (total_uih + total_targets);
-  return ctx + 2 * total_uih + total_targets;
 }
 
 }  // namespace hstu
@@ -526,12 +454,44 @@ using namespace hstu;
     default: { typedef float T; return CALL; }               \
   }
 
+// The argument checks that the forward and the backward of an op share, in the order both make them.  *empty: the call has
+// nothing to launch and the offsets were not looked at -- the caller returns HSTU_OK (the action backward after zero-filling
+// its tables, which is why `tables`, that d_table / d_target_table are there, is checked in front; the forward passes true).
+static int check_action_call(const char* what, ActionArgs* a, const int64_t* weights, int num_types, const int64_t* thresholds,
+                             const int64_t* threshold_weights, int num_thresholds, const void* uih_offsets,
+                             const void* target_offsets, int64_t total_uih_len, int64_t total_targets, int batch,
+                             int embedding_dim, int dtype, int index_dtype, bool tables, bool* empty) {
+  if (int e = fill_action_args(a, weights, num_types, thresholds, threshold_weights, num_thresholds, what)) return e;
+  if (int e = check_sizes(what, total_uih_len, total_targets, batch, embedding_dim, dtype, index_dtype)) return e;
+  if ((int64_t)num_types * embedding_dim > (1 << 24)) return set_error(HSTU_EINVAL, "%s: rows of more than 2^24 columns", what);
+  if (!tables) return set_error(HSTU_EINVAL, "%s: d_table / d_target_table are required", what);
+  *empty = batch == 0 || total_uih_len + total_targets == 0;
+  if (*empty) return HSTU_OK;
+  if (!uih_offsets || !target_offsets) return set_error(HSTU_EINVAL, "%s: the offsets are NULL", what);
+  return HSTU_OK;
+}
+
+static int check_combine_call(const char* what, int mode, int contextual_len, int64_t total_uih_len, int64_t total_targets,
+                              int batch, int dim, int dtype, int index_dtype, const void* seq_offsets, const void* out_offsets,
+                              const void* num_targets, int64_t* out_rows, bool* empty) {
+  if (mode != HSTU_COMBINE_SUM && mode != HSTU_COMBINE_INTERLEAVE_ALL && mode != HSTU_COMBINE_INTERLEAVE_UIH)
+    return set_error(HSTU_EINVAL, "%s: unknown mode %d", what, mode);
+  if (contextual_len < 0) return set_error(HSTU_EINVAL, "%s: negative contextual length", what);
+  if (int e = check_sizes(what, total_uih_len, total_targets, batch, dim, dtype, index_dtype)) return e;
+  *out_rows = combine_out_rows(mode, total_uih_len, total_targets, batch, contextual_len);
+  if (*out_rows > INT32_MAX) return set_error(HSTU_EINVAL, "%s: more than 2^31 - 1 output rows", what);
+  *empty = batch == 0 || *out_rows == 0;
+  if (*empty) return HSTU_OK;
+  if (!seq_offsets || !out_offsets) return set_error(HSTU_EINVAL, "%s: the offsets are NULL", what);
+  if (mode == HSTU_COMBINE_INTERLEAVE_UIH && !num_targets) return set_error(HSTU_EINVAL, "%s: INTERLEAVE_UIH needs num_targets", what);
+  return HSTU_OK;
+}
+
 extern "C" {
 
 size_t hstu_action_encode_bwd_workspace_bytes(int64_t total_rows, int32_t width) {
   (void)total_rows;
-  if (width <= 0) return 0;
-  return (size_t)kActionBwdGroupsMax * 2 * (size_t)width * sizeof(float);
+  return action_bwd_workspace_bytes(width);
 }
 
 int hstu_action_encode_fwd(const int64_t* actions, const int64_t* watchtimes, const void* uih_offsets, const void* target_offsets,
@@ -541,12 +501,12 @@ int hstu_action_encode_fwd(const int64_t* actions, const int64_t* watchtimes, co
                            int index_dtype, void* stream) {
   const char* what = "hstu_action_encode_fwd";
   ActionArgs a;
-  if (int e = fill_action_args(&a, weights, num_types, thresholds, threshold_weights, num_thresholds, what)) return e;
-  if (int e = check_sizes(what, total_uih_len, total_targets, batch, embedding_dim, dtype, index_dtype)) return e;
-  if ((int64_t)num_types * embedding_dim > (1 << 24)) return set_error(HSTU_EINVAL, "%s: rows of more than 2^24 columns", what);
+  bool empty;
+  if (int e = check_action_call(what, &a, weights, num_types, thresholds, threshold_weights, num_thresholds, uih_offsets,
+                                target_offsets, total_uih_len, total_targets, batch, embedding_dim, dtype, index_dtype, true, &empty))
+    return e;
+  if (empty) return HSTU_OK;
   const int64_t rows = total_uih_len + total_targets;
-  if (batch == 0 || rows == 0) return HSTU_OK;
-  if (!uih_offsets || !target_offsets) return set_error(HSTU_EINVAL, "%s: the offsets are NULL", what);
   if (!table || !target_table || !out || (total_uih_len > 0 && !actions) || (total_uih_len > 0 && num_thresholds > 0 && !watchtimes))
     return set_error(HSTU_EINVAL, "%s: NULL tensor", what);
   hipStream_t st = (hipStream_t)stream;
@@ -562,19 +522,19 @@ int hstu_action_encode_bwd(const void* d_out, const int64_t* actions, const int6
                            int dtype, int index_dtype, void* stream) {
   const char* what = "hstu_action_encode_bwd";
   ActionArgs a;
-  if (int e = fill_action_args(&a, weights, num_types, thresholds, threshold_weights, num_thresholds, what)) return e;
-  if (int e = check_sizes(what, total_uih_len, total_targets, batch, embedding_dim, dtype, index_dtype)) return e;
-  if ((int64_t)num_types * embedding_dim > (1 << 24)) return set_error(HSTU_EINVAL, "%s: rows of more than 2^24 columns", what);
-  if (!d_table || !d_target_table) return set_error(HSTU_EINVAL, "%s: d_table / d_target_table are required", what);
+  bool empty;
+  if (int e = check_action_call(what, &a, weights, num_types, thresholds, threshold_weights, num_thresholds, uih_offsets,
+                                target_offsets, total_uih_len, total_targets, batch, embedding_dim, dtype, index_dtype,
+                                d_table && d_target_table, &empty))
+    return e;
   hipStream_t st = (hipStream_t)stream;
   const int64_t rows = total_uih_len + total_targets;
   const size_t bytes = (size_t)num_types * embedding_dim * sizeof(float);
-  if (batch == 0 || rows == 0) {
+  if (empty) {
     hipError_t e = hipMemsetAsync(d_table, 0, bytes, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_target_table, 0, bytes, st);
     return e == hipSuccess ? HSTU_OK : set_error(HSTU_ELAUNCH, "%s: memset failed: %s", what, hipGetErrorString(e));
   }
-  if (!uih_offsets || !target_offsets) return set_error(HSTU_EINVAL, "%s: the offsets are NULL", what);
   if (!d_out || !workspace || (total_uih_len > 0 && !actions) || (total_uih_len > 0 && num_thresholds > 0 && !watchtimes))
     return set_error(HSTU_EINVAL, "%s: NULL tensor / workspace", what);
   const int is64 = index_dtype == HSTU_INDEX_I64;
@@ -587,15 +547,12 @@ int hstu_combine_embeddings_fwd(const void* content, const void* action, const v
                                 int64_t* out_timestamps, int64_t total_uih_len, int64_t total_targets, int32_t batch,
                                 int32_t contextual_len, int32_t dim, int mode, int dtype, int index_dtype, void* stream) {
   const char* what = "hstu_combine_embeddings_fwd";
-  if (mode != HSTU_COMBINE_SUM && mode != HSTU_COMBINE_INTERLEAVE_ALL && mode != HSTU_COMBINE_INTERLEAVE_UIH)
-    return set_error(HSTU_EINVAL, "%s: unknown mode %d", what, mode);
-  if (contextual_len < 0) return set_error(HSTU_EINVAL, "%s: negative contextual length", what);
-  if (int e = check_sizes(what, total_uih_len, total_targets, batch, dim, dtype, index_dtype)) return e;
-  const int64_t out_rows = combine_out_rows(mode, total_uih_len, total_targets, batch, contextual_len);
-  if (out_rows > INT32_MAX) return set_error(HSTU_EINVAL, "%s: more than 2^31 - 1 output rows", what);
-  if (batch == 0 || out_rows == 0) return HSTU_OK;
-  if (!seq_offsets || !out_offsets) return set_error(HSTU_EINVAL, "%s: the offsets are NULL", what);
-  if (mode == HSTU_COMBINE_INTERLEAVE_UIH && !num_targets) return set_error(HSTU_EINVAL, "%s: INTERLEAVE_UIH needs num_targets", what);
+  int64_t out_rows;
+  bool empty;
+  if (int e = check_combine_call(what, mode, contextual_len, total_uih_len, total_targets, batch, dim, dtype, index_dtype,
+                                 seq_offsets, out_offsets, num_targets, &out_rows, &empty))
+    return e;
+  if (empty) return HSTU_OK;
   if (mode != HSTU_COMBINE_SUM && !action) return set_error(HSTU_EINVAL, "%s: interleaving needs the action rows", what);
   const int64_t total = total_uih_len + total_targets;
   if (!out || !out_timestamps || (total > 0 && (!content || !timestamps)) || (contextual_len > 0 && !contextual))
@@ -611,15 +568,12 @@ int hstu_combine_embeddings_bwd(const void* d_out, const void* seq_offsets, cons
                                 int32_t batch, int32_t contextual_len, int32_t dim, int mode, int dtype, int index_dtype,
                                 void* stream) {
   const char* what = "hstu_combine_embeddings_bwd";
-  if (mode != HSTU_COMBINE_SUM && mode != HSTU_COMBINE_INTERLEAVE_ALL && mode != HSTU_COMBINE_INTERLEAVE_UIH)
-    return set_error(HSTU_EINVAL, "%s: unknown mode %d", what, mode);
-  if (contextual_len < 0) return set_error(HSTU_EINVAL, "%s: negative contextual length", what);
-  if (int e = check_sizes(what, total_uih_len, total_targets, batch, dim, dtype, index_dtype)) return e;
-  const int64_t out_rows = combine_out_rows(mode, total_uih_len, total_targets, batch, contextual_len);
-  if (out_rows > INT32_MAX) return set_error(HSTU_EINVAL, "%s: more than 2^31 - 1 output rows", what);
-  if (batch == 0 || out_rows == 0) return HSTU_OK;
-  if (!seq_offsets || !out_offsets) return set_error(HSTU_EINVAL, "%s: the offsets are NULL", what);
-  if (mode == HSTU_COMBINE_INTERLEAVE_UIH && !num_targets) return set_error(HSTU_EINVAL, "%s: INTERLEAVE_UIH needs num_targets", what);
+  int64_t out_rows;
+  bool empty;
+  if (int e = check_combine_call(what, mode, contextual_len, total_uih_len, total_targets, batch, dim, dtype, index_dtype,
+                                 seq_offsets, out_offsets, num_targets, &out_rows, &empty))
+    return e;
+  if (empty) return HSTU_OK;
   const int64_t total = total_uih_len + total_targets;
   if (!d_out || (total > 0 && !d_content)) return set_error(HSTU_EINVAL, "%s: NULL tensor", what);
   if (contextual_len == 0) d_contextual = nullptr;

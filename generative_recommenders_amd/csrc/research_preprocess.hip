@@ -19,11 +19,10 @@
 // dtype) that divides Do, Di and Dr and that the base pointers are aligned to.
 #include <math.h>
 
-#include <initializer_list>
-
 #include "hstu_common.cuh"
 #include "capi_internal.h"
 #include "drop_hash.cuh"
+#include "input_stage_dispatch.h"
 
 // every product and sum below is its own rounding (the fp32 path restates the reference's op-by-op chain bit for bit): no
 // FMA contraction in this file.  (__fmul_rn / __fadd_rn are plain operators in the HIP headers, parsed under the
@@ -32,6 +31,8 @@
 
 namespace hstu {
 namespace {
+using namespace input_stage;      // kThreads and every grid, slab count, piece width and workspace size: input_stage_dispatch.h
+static_assert(kLayoutPlain == HSTU_PREPROCESS_PLAIN, "input_stage_dispatch.h");
 
 HSTU_DEV float mul_rn(float a, float b) { return a * b; }
 HSTU_DEV float add_rn(float a, float b) { return a + b; }
@@ -47,14 +48,6 @@ HSTU_DEV T narrow(float x) {
   if constexpr (kPinned<T, V>) asm("" : "+v"(x));
   return (T)x;
 }
-
-constexpr int kThreads = 256;
-constexpr int kMaxUnitBlocks = 1024;      // grid.x cap; the pieces beyond are grid-strided
-constexpr int kFwdBlocks = 2048;          // 256 CUs x 8 resident workgroups
-constexpr int kBwdBlocks = 2048;
-constexpr int kBwdGroupsMax = 64;         // slabs of users whose d_pos partials the finish kernel adds
-constexpr int kBwdUsersPerGroupMin = 8;
-constexpr int kRatingGroupsMax = 256;
 
 template <typename T, int V> struct alignas(sizeof(T) * V) Pack { T e[V]; };
 template <typename T, int V> HSTU_DEV Pack<T, V> load_pack(const T* p) { return *reinterpret_cast<const Pack<T, V>*>(p); }
@@ -205,21 +198,18 @@ __global__ __launch_bounds__(kThreads) void input_preprocess_rating_bwd_kernel(c
                                                                                float* __restrict__ partial, const PreArgs a) {
   __shared__ float red[kThreads][V + 1];
   const int units = a.Dr / V;
-  int tpr = 1;
-  while (tpr < units && tpr < kThreads) tpr <<= 1;
-  const int rows_par = kThreads / tpr, lane = threadIdx.x % tpr, slot = threadIdx.x / tpr;
-  const int u = blockIdx.z * tpr + lane;
+  const RowSlots s = row_slots(units, kThreads);
+  const int u = blockIdx.z * s.tpr + s.lane;
   const bool live = u < units;
   const int c = u * V;
   const int want = blockIdx.y;
-  const int64_t rows = (int64_t)a.B * a.N;
-  const int64_t per = (rows + gridDim.x - 1) / gridDim.x;
-  const int64_t r0 = (int64_t)blockIdx.x * per, r1 = min(r0 + per, rows);
+  int64_t r0, r1;
+  slab_of((int64_t)a.B * a.N, &r0, &r1);
   float acc[V];
 #pragma unroll
   for (int i = 0; i < V; ++i) acc[i] = 0.f;
   if (live) {
-    for (int64_t r = r0 + slot; r < r1; r += rows_par) {
+    for (int64_t r = r0 + s.slot; r < r1; r += s.rows_par) {
       if (a.ids[r] == 0 || rating_of(a, r) != want) continue;
       // CONCAT: output row r, columns Di + c; INTERLEAVE: output row b 2N + 2n + 1 = 2r + 1, columns c
       const int64_t e0 = LAYOUT == HSTU_PREPROCESS_CONCAT ? r * a.Do + a.Di + c : (2 * r + 1) * a.Do + c;
@@ -236,12 +226,12 @@ __global__ __launch_bounds__(kThreads) void input_preprocess_rating_bwd_kernel(c
 #pragma unroll
   for (int i = 0; i < V; ++i) red[threadIdx.x][i] = acc[i];
   __syncthreads();
-  if (slot == 0 && live) {
+  if (s.slot == 0 && live) {
     float* dst = partial + ((int64_t)blockIdx.x * a.R + want) * a.Dr + c;
 #pragma unroll
     for (int i = 0; i < V; ++i) {
       float t = 0.f;
-      for (int k = 0; k < rows_par; ++k) t = add_rn(t, red[k * tpr + lane][i]);
+      for (int k = 0; k < s.rows_par; ++k) t = add_rn(t, red[k * s.tpr + s.lane][i]);
       dst[i] = t;
     }
   }
@@ -258,46 +248,7 @@ __global__ __launch_bounds__(kThreads) void input_preprocess_rating_finish_kerne
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-struct Dims {
-  int B, N, Nout, Di, Dr, Do, R, P, layout;
-};
-
-int unit_blocks(const Dims& d, int V) {
-  const int64_t units = (int64_t)d.Nout * (d.Do / V);
-  const int64_t b = (units + kThreads - 1) / kThreads;
-  return (int)(b > kMaxUnitBlocks ? kMaxUnitBlocks : (b < 1 ? 1 : b));
-}
-
-// the d_pos slabs: enough workgroups to fill the chip, at least kBwdUsersPerGroupMin users each (the partials are traffic).
-// Sized from the widest pieces (8 elements: the fewest unit blocks) whatever V is, so that the workspace size depends on the
-// shapes alone
-int bwd_groups(const Dims& d) {
-  int64_t ub = ((int64_t)d.Nout * d.Do + 8 * kThreads - 1) / (8 * kThreads);
-  ub = ub > kMaxUnitBlocks ? kMaxUnitBlocks : (ub < 1 ? 1 : ub);
-  int g = (int)((kBwdBlocks + ub - 1) / ub);
-  const int by_users = (d.B + kBwdUsersPerGroupMin - 1) / kBwdUsersPerGroupMin;
-  if (g > by_users) g = by_users;
-  if (g > kBwdGroupsMax) g = kBwdGroupsMax;
-  return g < 1 ? 1 : g;
-}
-
-// B users in at most `groups` slabs of *users_per_group: the number of slabs
-int slab_count(int B, int groups, int* users_per_group) {
-  *users_per_group = (B + groups - 1) / groups;
-  return (B + *users_per_group - 1) / *users_per_group;
-}
-
-int rating_groups(const Dims& d) {
-  int64_t g = ((int64_t)d.B * d.N + 63) / 64;
-  if (g > kRatingGroupsMax) g = kRatingGroupsMax;
-  return g < 1 ? 1 : (int)g;
-}
-
-size_t pos_partial_bytes(const Dims& d) { return align256((size_t)bwd_groups(d) * d.Nout * d.Do * sizeof(float)); }
-size_t rating_partial_bytes(const Dims& d) {
-  return d.layout == HSTU_PREPROCESS_PLAIN ? 0 : align256((size_t)rating_groups(d) * d.R * d.Dr * sizeof(float));
-}
-
+// (Dims and everything decided from it: input_stage_dispatch.h)
 int fill_dims(Dims* d, const char* what, int batch, int n, int item_dim, int rating_dim, int num_positions, int num_ratings,
               int layout) {
   if (layout != HSTU_PREPROCESS_PLAIN && layout != HSTU_PREPROCESS_CONCAT && layout != HSTU_PREPROCESS_INTERLEAVE)
@@ -348,31 +299,12 @@ PreArgs make_args(const Dims& d, const int64_t* ids, const void* ratings, int ra
   return a;
 }
 
-bool aligned_to(size_t bytes, std::initializer_list<const void*> ptrs) {
-  for (const void* p : ptrs)
-    if (p && ((uintptr_t)p & (bytes - 1))) return false;
-  return true;
-}
-
-// the widest piece: at most 16 bytes of the output dtype, dividing every row width, every base pointer aligned to it
-int pick_vec(const Dims& d, size_t emb_size, size_t out_size, std::initializer_list<const void*> emb_ptrs,
-             std::initializer_list<const void*> out_ptrs) {
-  for (int V = (int)(16 / out_size); V > 1; V >>= 1) {
-    if (d.Do % V || d.Di % V || (d.layout != HSTU_PREPROCESS_PLAIN && d.Dr % V)) continue;
-    if (!aligned_to(V * emb_size, emb_ptrs) || !aligned_to(V * out_size, out_ptrs)) continue;
-    return V;
-  }
-  return 1;
-}
-
 template <typename TE, typename TO, int LAYOUT, int V>
 int fwd_launch(const Dims& d, const PreArgs& a, const void* emb, const void* pos, const void* rat, void* out, float* valid,
                hipStream_t st) {
   const int gx = unit_blocks(d, V);
-  int groups = (kFwdBlocks + gx - 1) / gx;
-  if (groups > d.B) groups = d.B;
   int upg;
-  const dim3 grid(gx, slab_count(d.B, groups, &upg));
+  const dim3 grid(gx, slab_count(d.B, fwd_user_groups(d, gx), &upg));
   hipLaunchKernelGGL((input_preprocess_fwd_kernel<TE, TO, LAYOUT, V>), grid, dim3(kThreads), 0, st, (const TE*)emb,
                      (const TO*)pos, (const TO*)rat, (TO*)out, valid, a, upg);
   return check_launch("hstu_input_preprocess_fwd");
@@ -381,13 +313,7 @@ int fwd_launch(const Dims& d, const PreArgs& a, const void* emb, const void* pos
 template <typename TE, typename TO, int LAYOUT, int V>
 int bwd_launch(const Dims& d, const PreArgs& a, const void* g, void* d_emb, float* partial, hipStream_t st) {
   const int gx = unit_blocks(d, V);
-  int groups;
-  if (partial) {
-    groups = bwd_groups(d);
-  } else {
-    groups = (kFwdBlocks + gx - 1) / gx;
-    if (groups > d.B) groups = d.B;
-  }
+  const int groups = partial ? bwd_groups(d) : fwd_user_groups(d, gx);
   int upg;
   const dim3 grid(gx, slab_count(d.B, groups, &upg));       // grid.y <= groups: the workspace holds `groups` slabs
   hipLaunchKernelGGL((input_preprocess_bwd_kernel<TE, TO, LAYOUT, V>), grid, dim3(kThreads), 0, st, (const TO*)g, (TE*)d_emb,
@@ -397,10 +323,7 @@ int bwd_launch(const Dims& d, const PreArgs& a, const void* g, void* d_emb, floa
 
 template <typename TO, int LAYOUT, int V>
 int rating_launch(const Dims& d, const PreArgs& a, const void* g, float* partial, hipStream_t st) {
-  const int units = d.Dr / V;
-  int tpr = 1;
-  while (tpr < units && tpr < kThreads) tpr <<= 1;
-  const dim3 grid(rating_groups(d), d.R, (units + tpr - 1) / tpr);
+  const dim3 grid(rating_groups(d), d.R, rating_grid_z(d, V));
   hipLaunchKernelGGL((input_preprocess_rating_bwd_kernel<TO, LAYOUT, V>), grid, dim3(kThreads), 0, st, (const TO*)g, partial, a);
   return check_launch("hstu_input_preprocess_bwd(rating)");
 }
@@ -535,18 +458,16 @@ int hstu_input_preprocess_bwd(const void* d_out, const int64_t* past_ids, const 
   }
   if (d_pos_table) {
     const int64_t width = (int64_t)d.Nout * d.Do, total = (int64_t)d.P * d.Do;
-    int64_t blocks = (total + kThreads - 1) / kThreads;
-    if (blocks > kFwdBlocks) blocks = kFwdBlocks;
     int upg;
     const int gy = slab_count(d.B, bwd_groups(d), &upg);
-    hipLaunchKernelGGL(input_preprocess_pos_finish_kernel, dim3((int)blocks), dim3(kThreads), 0, st, pos_partial, gy, width, total,
-                       d_pos_table);
+    hipLaunchKernelGGL(input_preprocess_pos_finish_kernel, dim3(pos_finish_blocks(total)), dim3(kThreads), 0, st, pos_partial, gy,
+                       width, total, d_pos_table);
     if (int e = check_launch("hstu_input_preprocess_bwd(pos finish)")) return e;
   }
   if (d_rating_table) {
     if (int e = rating_dispatch(d, a, V, out_dtype, d_out, rating_partial, st)) return e;
     const int width = d.R * d.Dr;
-    hipLaunchKernelGGL(input_preprocess_rating_finish_kernel, dim3((width + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
+    hipLaunchKernelGGL(input_preprocess_rating_finish_kernel, dim3(rating_finish_blocks(width)), dim3(kThreads), 0, st,
                        rating_partial, rating_groups(d), width, a.s, d_rating_table);
     if (int e = check_launch("hstu_input_preprocess_bwd(rating finish)")) return e;
   }

@@ -3,8 +3,9 @@ of calls, each labelled with the class it is MEANT to reach -- the lines of thos
 walks many rows (the slab loop, the user advance, the wrapped lane loop, the second grid dimension, the clamps of the slab
 counts, the grid stride).  tests/test_input_stage_classes_gpu.py runs every row on the GPU through the C ABI, with outputs
 and workspaces it owns; tests/test_input_stage_classes_host.py checks without a GPU that every row lands on its label under
-the restatement of the host geometry below (at 256, 64 and 304 CUs), that every label is used, and that the restated
-constants are the ones in the .hip sources.
+the restatement of the host geometry below (at 256, 64 and 304 CUs), that every label is used, and that the restatement
+answers what csrc/input_stage_dispatch.h and csrc/row_slots.h -- the host geometry of the two units, compiled alone --
+answer, for every row and for a sweep around every constant.
 
 Layout shared by both: every output and workspace lives alone in a sentinel-filled byte allocation (256-byte aligned),
 GUARD bytes from its start plus the bytes ``mis`` lists for its role; GUARD more bytes follow it.
@@ -23,6 +24,18 @@ ELEM_BYTES = {BF16: 2, F16: 2, F32: 4}
 SUM, INTERLEAVE_ALL, INTERLEAVE_UIH = 0, 1, 2          # HSTU_COMBINE_*
 PLAIN, CONCAT, INTERLEAVE = 0, 1, 2                    # HSTU_PREPROCESS_*
 
+# ------------------------------------------------------------------------------------------------ row_slots.h
+def threads_per_row(units, threads):
+    tpr = 1
+    while tpr < units and tpr < threads:
+        tpr <<= 1
+    return tpr
+
+
+def rows_in_flight(units, threads):
+    return threads // threads_per_row(units, threads)
+
+
 # ------------------------------------------------------------------------------------------------ preprocess_ops.hip
 K_PRE_THREADS = 256               # kPreThreads
 K_PRE_BLOCKS_PER_CU = 8           # kPreBlocksPerCu
@@ -36,10 +49,7 @@ def ceil_div(a, b):
 
 
 def host_tpr(units):
-    tpr = 1
-    while tpr < units and tpr < K_PRE_THREADS:
-        tpr <<= 1
-    return tpr
+    return threads_per_row(units, K_PRE_THREADS)
 
 
 def host_rows_par(units):
@@ -65,6 +75,14 @@ def action_bwd_groups(rows, units, cus):
 
 def action_bwd_grid_y(units):
     return ceil_div(units, K_PRE_THREADS)
+
+
+def action_bwd_finish_blocks(width):
+    return ceil_div(2 * width, 256)
+
+
+def action_bwd_workspace_bytes(width):
+    return K_ACTION_BWD_GROUPS_MAX * 2 * width * 4 if width > 0 else 0
 
 
 def pre_pick_vec(row_elems, dtype, any_misaligned):
@@ -131,21 +149,27 @@ def rating_groups(batch, n):
 
 
 def rating_tpr(dr, v):
-    units, tpr = dr // v, 1
-    while tpr < units and tpr < K_THREADS:
-        tpr <<= 1
-    return tpr
+    return threads_per_row(dr // v, K_THREADS)
 
 
 def rating_grid_z(dr, v):
     return ceil_div(dr // v, rating_tpr(dr, v))
 
 
-def research_pick_vec(layout, di, dr, emb_dtype, out_dtype, emb_offsets, out_offsets):
+def pos_finish_blocks(total):
+    return min(ceil_div(total, K_THREADS), K_FWD_BLOCKS)
+
+
+def rating_finish_blocks(width):
+    return ceil_div(width, K_THREADS)
+
+
+def research_pick_vec(layout, di, dr, emb_dtype, out_dtype, emb_offsets, out_offsets, do=None):
     """pick_vec of research_preprocess.hip: the widest of 8 / 4 / 2 / 1 elements (at most 16 bytes of the output dtype) that
     divides Do, Di (and Dr in the rated layouts) and that every base pointer is aligned to -- the embedding-typed ones to
-    V * sizeof(emb), the others to V * sizeof(out).  ``*_offsets``: byte offsets of the pointers from 256-byte alignment"""
-    do = d_out_of(layout, di, dr)
+    V * sizeof(emb), the others to V * sizeof(out).  ``*_offsets``: byte offsets of the pointers from 256-byte alignment.
+    ``do``: an output width other than the layout's (no call has one; it tells the three divisibility checks apart)"""
+    do = d_out_of(layout, di, dr) if do is None else do
     es, osz = ELEM_BYTES[emb_dtype], ELEM_BYTES[out_dtype]
     v = 16 // osz
     while v > 1:
