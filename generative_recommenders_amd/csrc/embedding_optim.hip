@@ -23,6 +23,11 @@
 // Every segment is finished by exactly one owner before its state is touched; there are no float atomics; the order of
 // summation is a function of the sorted positions alone (never of timing or of the grid size), so results are
 // bit-identical from run to run.
+//
+// hstu_embedding_grad_coalesce runs the same three steps with another ending (the kernels' Sink): a finished segment is not
+// applied to the table but written out, scale * G[r, :] and r, at the segment's rank among the segment heads -- the short
+// list a data-parallel rank exchanges (ops/embedding.py).  The rank comes from an inclusive scan over the head flags of the
+// sorted positions (three small kernels in front of the chunk kernel); the sums are the update's, addition for addition.
 #include "hstu_common.cuh"
 #include "capi_internal.h"
 #include "embedding_sort.cuh"
@@ -74,11 +79,17 @@ __device__ __forceinline__ void add_row(float (&acc)[NP][VEC], const float (&v)[
     }
 }
 
-// the update of one finished segment: acc = G[r, :], w = W[r, :] (loaded by the caller ahead of time), m_old =
-// momentum1[r].  The squares are added pairwise inside the lane and by a butterfly across the wave: log2(dim) levels.
+// sum_d G[r, d]^2 of the row in acc, in every lane.  ONE tree for every row layout, so that the same G gives the same bits
+// whether it is summed from 16-bit rows (8 columns per lane and piece) or read back as an fp32 row (4 columns per lane and
+// piece: the coalesced lists of replicated tables) -- and whichever kernel finishes the segment: every square is rounded
+// on its own (no contraction into a fused multiply-add, which the compiler would choose per kernel), then added
+// pairwise over the 8 columns of a group g = column / 8, then over the groups by the bits of g: 6, 7 (the lane's pieces,
+// 64 groups apart), then 5 .. 0 (the butterfly across the wave).  An fp32 lane holds half a group; lane m, piece j is the
+// half b = m & 1 of group (m >> 1) + 32 j: bit 5 of g is bit 0 of j, bits 6 and 7 are bits 1 and 2 of j.  Absent columns add 0.
 template <int VEC, int NP>
-__device__ __forceinline__ void apply_update(const float (&acc)[NP][VEC], float (&w)[NP][VEC], float m_old, int lane, int pieces, int dim,
-                                             float* __restrict__ w_row, float* __restrict__ m_ptr, float lr, float eps) {
+__device__ __forceinline__ float row_sum_of_squares(const float (&acc)[NP][VEC], int lane, int pieces) {
+#pragma clang fp contract(off)
+  static_assert(VEC == 4 || VEC == 8, "16-byte pieces of fp32 or 16-bit columns");
   float sq[NP][VEC];
 #pragma unroll
   for (int j = 0; j < NP; ++j) {
@@ -92,13 +103,33 @@ __device__ __forceinline__ void apply_update(const float (&acc)[NP][VEC], float 
     for (int j = 0; j < NP; ++j)
 #pragma unroll
       for (int c = 0; c + s < VEC; c += 2 * s) sq[j][c] += sq[j][c + s];
+  if constexpr (VEC == 4) {
 #pragma unroll
-  for (int s = 1; s < NP; s *= 2)
+    for (int j = 0; j < NP; ++j) sq[j][0] += __shfl_xor(sq[j][0], 1);     // the two halves of a group
 #pragma unroll
-    for (int j = 0; j + s < NP; j += 2 * s) sq[j][0] += sq[j + s][0];
+    for (int s = 2; s < NP; s *= 2)                 // bits 6, 7 of g
+#pragma unroll
+      for (int j = 0; j < NP; ++j)
+        if ((j & (2 * s - 2)) == 0 && j + s < NP) sq[j][0] += sq[j + s][0];
+    if (NP > 1) sq[0][0] += sq[1][0];               // bit 5
+  } else {
+#pragma unroll
+    for (int s = 1; s < NP; s *= 2)
+#pragma unroll
+      for (int j = 0; j + s < NP; j += 2 * s) sq[j][0] += sq[j + s][0];
+  }
   float ss = sq[0][0];
 #pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off);
+  for (int off = 32; off >= (VEC == 4 ? 2 : 1); off >>= 1) ss += __shfl_xor(ss, off);
+  return ss;
+}
+
+// the update of one finished segment: acc = G[r, :], w = W[r, :] (loaded by the caller ahead of time), m_old =
+// momentum1[r].
+template <int VEC, int NP>
+__device__ __forceinline__ void apply_update(const float (&acc)[NP][VEC], float (&w)[NP][VEC], float m_old, int lane, int pieces, int dim,
+                                             float* __restrict__ w_row, float* __restrict__ m_ptr, float lr, float eps) {
+  const float ss = row_sum_of_squares<VEC, NP>(acc, lane, pieces);
   const float m_new = m_old + ss / (float)dim;
   const float step = lr / (sqrtf(m_new) + eps);
 #pragma unroll
@@ -109,11 +140,37 @@ __device__ __forceinline__ void apply_update(const float (&acc)[NP][VEC], float 
   if (lane == 0) *m_ptr = m_new;
 }
 
-template <typename T, int NP, int U, int kChunk>
+// What the chunk and combine kernels do with a finished segment: apply it to the table (the update) ...
+struct ApplySink {
+  static constexpr bool kApply = true;
+  float *weight, *momentum1;
+  float lr, eps;
+};
+// ... or write it out (the coalesce): rank[p] = number of segment heads among the sorted positions 0 .. p, the same for
+// every position of a segment, so any of them names the segment's slot rank[p] - 1
+struct EmitSink {
+  static constexpr bool kApply = false;
+  int32_t* rows;
+  float* G;
+  const int32_t* rank;
+  float scale;
+};
+
+template <int VEC, int NP>
+__device__ __forceinline__ void emit_segment(const float (&acc)[NP][VEC], int lane, int pieces, int dim, const EmitSink& s, int id, int slot) {
+  float out[NP][VEC];
+#pragma unroll
+  for (int j = 0; j < NP; ++j)
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) out[j][c] = s.scale * acc[j][c];
+  store_f32_row<VEC, NP>(s.G + (int64_t)slot * dim, lane, pieces, out);
+  if (lane == 0) s.rows[slot] = id;
+}
+
+template <typename T, int NP, int U, int kChunk, typename Sink>
 __global__ __launch_bounds__(kOptWaves * 64) void adagrad_chunk_kernel(const T* __restrict__ g, const int32_t* __restrict__ perm,
                                                                        const int32_t* __restrict__ sorted_idx, int64_t n, int dim,
-                                                                       float* __restrict__ weight, float* __restrict__ momentum1,
-                                                                       float* __restrict__ partials, float lr, float eps) {
+                                                                       float* __restrict__ partials, Sink sink) {
   constexpr int VEC = 16 / (int)sizeof(T);
   const int lane = threadIdx.x & 63;
   const int64_t waves = (int64_t)gridDim.x * kOptWaves;
@@ -145,7 +202,7 @@ __global__ __launch_bounds__(kOptWaves * 64) void adagrad_chunk_kernel(const T* 
     for (int r0 = 0; r0 < cnt; r0 += U) {
       u32x4 v[U][NP];
       float w[U][NP][VEC], m_old[U];
-      int id[U];
+      int id[U], slot[U];
       bool ends[U], whole[U];
       bool began_before = open_left;                // of the segment that row u belongs to
 #pragma unroll
@@ -164,9 +221,14 @@ __global__ __launch_bounds__(kOptWaves * 64) void adagrad_chunk_kernel(const T* 
           if (p < pieces) v[u][j] = *(const u32x4*)(row + 16 * p);
         }
         m_old[u] = 0.f;
-        if (whole[u]) {                             // the table row travels with the gradient rows
-          load_f32_row<VEC, NP>(weight + (int64_t)id[u] * dim, lane, pieces, w[u]);
-          m_old[u] = momentum1[id[u]];
+        slot[u] = 0;
+        if constexpr (Sink::kApply) {
+          if (whole[u]) {                           // the table row travels with the gradient rows
+            load_f32_row<VEC, NP>(sink.weight + (int64_t)id[u] * dim, lane, pieces, w[u]);
+            m_old[u] = sink.momentum1[id[u]];
+          }
+        } else {
+          if (whole[u]) slot[u] = sink.rank[c0 + q] - 1;   // so does the segment's slot
         }
       }
 #pragma unroll
@@ -182,7 +244,11 @@ __global__ __launch_bounds__(kOptWaves * 64) void adagrad_chunk_kernel(const T* 
         }
         if (ends[u]) {
           if (whole[u]) {
-            apply_update<VEC, NP>(acc, w[u], m_old[u], lane, pieces, dim, weight + (int64_t)id[u] * dim, momentum1 + id[u], lr, eps);
+            if constexpr (Sink::kApply)
+              apply_update<VEC, NP>(acc, w[u], m_old[u], lane, pieces, dim, sink.weight + (int64_t)id[u] * dim, sink.momentum1 + id[u],
+                                    sink.lr, sink.eps);
+            else
+              emit_segment<VEC, NP>(acc, lane, pieces, dim, sink, id[u], slot[u]);
           } else {
             store_f32_row<VEC, NP>(partials + (2 * b + (open_left ? 0 : 1)) * dim, lane, pieces, acc);
           }
@@ -201,12 +267,11 @@ __global__ __launch_bounds__(kOptWaves * 64) void adagrad_chunk_kernel(const T* 
 // its head lies in this chunk.  Its partial sums, in position order: slot (b, 1), then slot (k, 0) of every following chunk
 // k up to the first one the segment does not leave.  Wave w adds the w-th share of that list; wave 0 adds the shares in wave
 // order.  (Every condition below is the same in all threads of the workgroup: the barriers are reached by all or none.)
-template <int VEC, int NP, int kChunk>
+template <int VEC, int NP, int kChunk, typename Sink>
 __global__ __launch_bounds__(kCombineWaves * 64) void adagrad_combine_kernel(const int32_t* __restrict__ sorted_idx, int64_t n, int dim,
-                                                                             float* __restrict__ weight, float* __restrict__ momentum1,
-                                                                             const float* __restrict__ partials, float lr, float eps) {
+                                                                             const float* __restrict__ partials, Sink sink) {
   extern __shared__ __attribute__((aligned(16))) float shares[];       // (kCombineWaves - 1) rows of dim floats
-  constexpr int U = NP * VEC >= 32 ? 2 : NP * VEC >= 16 ? 4 : 8;   // partial sums in flight: 64 registers
+  constexpr int U = NP >= 8 ? 1 : NP * VEC >= 32 ? 2 : NP * VEC >= 16 ? 4 : 8;   // partial sums in flight: 64 registers (32 in eight pieces)
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int64_t chunks = (n + kChunk - 1) / kChunk;
@@ -231,12 +296,16 @@ __global__ __launch_bounds__(kCombineWaves * 64) void adagrad_combine_kernel(con
     const int64_t total = last - b + 1;                      // list item 0: slot (b, 1); item i > 0: slot (b + i, 0)
     const int64_t share = (total + kCombineWaves - 1) / kCombineWaves;
     const int64_t i0 = wave * share, i1 = min(total, i0 + share);
-    float* w_row = weight + (int64_t)id * dim;
     float w[NP][VEC], acc[NP][VEC];
     float m_old = 0.f;
+    int slot = 0;
     if (wave == 0) {
-      load_f32_row<VEC, NP>(w_row, lane, pieces, w);
-      m_old = momentum1[id];
+      if constexpr (Sink::kApply) {
+        load_f32_row<VEC, NP>(sink.weight + (int64_t)id * dim, lane, pieces, w);
+        m_old = sink.momentum1[id];
+      } else {
+        slot = sink.rank[c1 - 1] - 1;
+      }
     }
 #pragma unroll
     for (int j = 0; j < NP; ++j)
@@ -258,14 +327,115 @@ __global__ __launch_bounds__(kCombineWaves * 64) void adagrad_combine_kernel(con
     if (wave > 0) store_f32_row<VEC, NP>(shares + (int64_t)(wave - 1) * dim, lane, pieces, acc);
     __syncthreads();
     if (wave == 0) {
+      constexpr int kShareUnroll = NP >= 8 ? 1 : kCombineWaves - 1;   // eight pieces: one share at a time, or the row's registers spill
+#pragma unroll kShareUnroll
       for (int s = 0; s < kCombineWaves - 1; ++s) {
         float v[NP][VEC];
         load_f32_row<VEC, NP>(shares + (int64_t)s * dim, lane, pieces, v);
         add_row<VEC, NP>(acc, v, lane, pieces);
       }
-      apply_update<VEC, NP>(acc, w, m_old, lane, pieces, dim, w_row, momentum1 + id, lr, eps);
+      if constexpr (Sink::kApply)
+        apply_update<VEC, NP>(acc, w, m_old, lane, pieces, dim, sink.weight + (int64_t)id * dim, sink.momentum1 + id, sink.lr, sink.eps);
+      else
+        emit_segment<VEC, NP>(acc, lane, pieces, dim, sink, id, slot);
     }
     __syncthreads();                                         // the shares are read before the next segment's are written
+  }
+}
+
+// ---- the coalesce's slots: rank[p] = number of segment heads among the sorted positions 0 .. p (an inclusive scan of the
+// head flags; integers, so any order gives the same result).  Tiles of kScanTile positions: count the heads per tile,
+// scan the tile counts in one workgroup (which also knows the total: *count), scan every tile from its offset.
+constexpr int kScanThreads = 256;
+constexpr int kScanItems = 8;          // consecutive positions per thread: two 16-byte stores of ranks
+constexpr int kScanTile = kScanThreads * kScanItems;
+constexpr int kTileScanThreads = 1024;
+
+// exclusive scan of one value per thread across the workgroup (THREADS / 64 waves); total: the sum, in every thread
+template <int THREADS>
+__device__ __forceinline__ int block_exclusive_scan(int v, int* wave_sums, int& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = v;
+#pragma unroll
+  for (int off = 1; off < 64; off *= 2) {
+    const int t = __shfl_up(incl, off);
+    if (lane >= off) incl += t;
+  }
+  if (lane == 63) wave_sums[wave] = incl;
+  __syncthreads();
+  int before = 0;
+  total = 0;
+#pragma unroll
+  for (int w = 0; w < THREADS / 64; ++w) {
+    const int s = wave_sums[w];
+    before += w < wave ? s : 0;
+    total += s;
+  }
+  __syncthreads();                                  // wave_sums is written again by the caller's next round
+  return before + incl - v;
+}
+
+// the head flags of the thread's kScanItems positions from p0 on (positions >= n: 0); returns their sum
+__device__ __forceinline__ int head_flags(const int32_t* __restrict__ sorted_idx, int64_t n, int64_t p0, int (&flag)[kScanItems]) {
+  int prev = p0 > 0 && p0 <= n ? sorted_idx[p0 - 1] : -1;          // ids are >= 0: position 0 is a head
+  int sum = 0;
+#pragma unroll
+  for (int i = 0; i < kScanItems; ++i) {
+    const bool live = p0 + i < n;
+    const int id = live ? sorted_idx[p0 + i] : prev;
+    flag[i] = live && id != prev;
+    sum += flag[i];
+    prev = id;
+  }
+  return sum;
+}
+
+__global__ __launch_bounds__(kScanThreads) void head_count_kernel(const int32_t* __restrict__ sorted_idx, int64_t n, int64_t tiles,
+                                                                  int32_t* __restrict__ tile_heads) {
+  __shared__ int wave_sums[kScanThreads / 64];
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    int flag[kScanItems], total;
+    const int mine = head_flags(sorted_idx, n, t * kScanTile + (int64_t)threadIdx.x * kScanItems, flag);
+    (void)block_exclusive_scan<kScanThreads>(mine, wave_sums, total);
+    if (threadIdx.x == 0) tile_heads[t] = total;
+  }
+}
+
+// one workgroup, in place: tile_heads[t] -> the heads in front of tile t; *count = all of them
+__global__ __launch_bounds__(kTileScanThreads) void tile_offsets_kernel(int32_t* __restrict__ tile_heads, int64_t tiles,
+                                                                        int32_t* __restrict__ count) {
+  __shared__ int wave_sums[kTileScanThreads / 64];
+  int carry = 0;
+  for (int64_t t0 = 0; t0 < tiles; t0 += kTileScanThreads) {
+    const int64_t t = t0 + threadIdx.x;
+    const int v = t < tiles ? tile_heads[t] : 0;
+    int total;
+    const int before = block_exclusive_scan<kTileScanThreads>(v, wave_sums, total);
+    if (t < tiles) tile_heads[t] = carry + before;
+    carry += total;
+  }
+  if (threadIdx.x == 0) *count = carry;
+}
+
+__global__ __launch_bounds__(kScanThreads) void head_rank_kernel(const int32_t* __restrict__ sorted_idx, int64_t n, int64_t tiles,
+                                                                 const int32_t* __restrict__ tile_offsets, int32_t* __restrict__ rank) {
+  __shared__ int wave_sums[kScanThreads / 64];
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const int64_t p0 = t * kScanTile + (int64_t)threadIdx.x * kScanItems;
+    int flag[kScanItems], total;
+    const int mine = head_flags(sorted_idx, n, p0, flag);
+    int r = tile_offsets[t] + block_exclusive_scan<kScanThreads>(mine, wave_sums, total);
+    int out[kScanItems];
+#pragma unroll
+    for (int i = 0; i < kScanItems; ++i) out[i] = r += flag[i];
+    if (p0 + kScanItems <= n) {                     // rank is 256-byte aligned and p0 a multiple of 8: 16-byte stores
+#pragma unroll
+      for (int i = 0; i < kScanItems; i += 4) *(int4*)(rank + p0 + i) = *(const int4*)&out[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < kScanItems; ++i)
+        if (p0 + i < n) rank[p0 + i] = out[i];
+    }
   }
 }
 
@@ -290,45 +460,83 @@ static OptLayout opt_layout(int64_t n, int table_rows) {
   return l;
 }
 
+// the update's workspace | rank (n) | heads per scan tile
+struct CoalesceLayout {
+  OptLayout opt;
+  size_t rank_off, tiles_off, total;
+};
+
+static CoalesceLayout coalesce_layout(int64_t n, int table_rows) {
+  CoalesceLayout l;
+  l.opt = opt_layout(n, table_rows);
+  l.rank_off = l.opt.total;
+  l.tiles_off = l.rank_off + align256((size_t)n * sizeof(int32_t));
+  l.total = l.tiles_off + align256((size_t)((n + kScanTile - 1) / kScanTile) * sizeof(int32_t));
+  return l;
+}
+
+static int launch_head_ranks(const int32_t* sorted_idx, int64_t n, int32_t* tile_heads, int32_t* rank, int32_t* count, hipStream_t st,
+                             const char* what) {
+  const int64_t tiles = (n + kScanTile - 1) / kScanTile;
+  const dim3 grid((unsigned)(tiles < kOptMaxBlocks ? tiles : kOptMaxBlocks));
+  hipLaunchKernelGGL(head_count_kernel, grid, dim3(kScanThreads), 0, st, sorted_idx, n, tiles, tile_heads);
+  if (int rc = check_launch(what)) return rc;
+  hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(kTileScanThreads), 0, st, tile_heads, tiles, count);
+  if (int rc = check_launch(what)) return rc;
+  hipLaunchKernelGGL(head_rank_kernel, grid, dim3(kScanThreads), 0, st, sorted_idx, n, tiles, (const int32_t*)tile_heads, rank);
+  return check_launch(what);
+}
+
 struct OptArgs {
   const void* g;
   const int32_t *perm, *sorted_idx;
   int64_t n;
   int dim;
-  float *weight, *momentum1, *partials;
-  float lr, eps;
+  float* partials;
   hipStream_t st;
 };
 
-template <typename T, int NP, int U, int kChunk>
-static int opt_launch_chunk(const OptArgs& a, const char* what) {
+template <typename T, int NP, int U, int kChunk, typename Sink>
+static int opt_launch_chunk(const OptArgs& a, const Sink& sink, const char* what) {
   constexpr int VEC = 16 / (int)sizeof(T);
   const int64_t chunks = (a.n + kChunk - 1) / kChunk;
   const int64_t blocks = (chunks + kOptWaves - 1) / kOptWaves;
-  hipLaunchKernelGGL((adagrad_chunk_kernel<T, NP, U, kChunk>), dim3((unsigned)(blocks < kOptMaxBlocks ? blocks : kOptMaxBlocks)),
-                     dim3(kOptWaves * 64), 0, a.st, (const T*)a.g, a.perm, a.sorted_idx, a.n, a.dim, a.weight, a.momentum1, a.partials,
-                     a.lr, a.eps);
+  hipLaunchKernelGGL((adagrad_chunk_kernel<T, NP, U, kChunk, Sink>), dim3((unsigned)(blocks < kOptMaxBlocks ? blocks : kOptMaxBlocks)),
+                     dim3(kOptWaves * 64), 0, a.st, (const T*)a.g, a.perm, a.sorted_idx, a.n, a.dim, a.partials, sink);
   if (int rc = check_launch(what)) return rc;
   if (chunks < 2) return HSTU_OK;                                          // one chunk: nothing can leave it
   const size_t lds = (size_t)(kCombineWaves - 1) * a.dim * sizeof(float);  // at most 56 KiB
-  hipLaunchKernelGGL((adagrad_combine_kernel<VEC, NP, kChunk>), dim3((unsigned)(chunks - 1 < kOptMaxBlocks ? chunks - 1 : kOptMaxBlocks)),
-                     dim3(kCombineWaves * 64), lds, a.st, a.sorted_idx, a.n, a.dim, a.weight, a.momentum1, a.partials, a.lr, a.eps);
+  hipLaunchKernelGGL((adagrad_combine_kernel<VEC, NP, kChunk, Sink>), dim3((unsigned)(chunks - 1 < kOptMaxBlocks ? chunks - 1 : kOptMaxBlocks)),
+                     dim3(kCombineWaves * 64), lds, a.st, a.sorted_idx, a.n, a.dim, a.partials, sink);
   return check_launch(what);
 }
 
-template <typename T, int NP, int U>
-static int opt_launch(const OptArgs& a, const char* what) {
-  return opt_chunk(a.n, a.dim) == kChunkSmall ? opt_launch_chunk<T, NP, U, kChunkSmall>(a, what) : opt_launch_chunk<T, NP, U, kChunkLarge>(a, what);
+template <typename T, int NP, int U, typename Sink>
+static int opt_launch(const OptArgs& a, const Sink& sink, const char* what) {
+  return opt_chunk(a.n, a.dim) == kChunkSmall ? opt_launch_chunk<T, NP, U, kChunkSmall>(a, sink, what)
+                                              : opt_launch_chunk<T, NP, U, kChunkLarge>(a, sink, what);
 }
 
 // gradient rows in flight per wave: eight for rows of up to 1 KiB (the reference's dim 256 in any dtype), fewer for wider
 // rows -- each comes with a table row of twice (16-bit dout) or once its size in registers
-template <typename T>
-static int opt_dispatch(const OptArgs& a, const char* what) {
+// (the coalesce keeps them: the groups do not change the order of a sum, and one rule is one thing less to test)
+template <typename T, typename Sink>
+static int opt_dispatch(const OptArgs& a, const Sink& sink, const char* what) {
   const int row_bytes = a.dim * (int)sizeof(T);
-  if (row_bytes <= 1024) return opt_launch<T, 1, 8>(a, what);
-  if (row_bytes <= 2048) return opt_launch<T, 2, 4>(a, what);
-  return opt_launch<T, 4, (sizeof(T) == 2 ? 2 : 4)>(a, what);
+  if (row_bytes <= 1024) return opt_launch<T, 1, 8>(a, sink, what);
+  if (row_bytes <= 2048) return opt_launch<T, 2, 4>(a, sink, what);
+  if constexpr (sizeof(T) == 4 && Sink::kApply)     // coalesced fp32 rows of tables wider than 1024 columns: 8 KiB
+    if (row_bytes > 4096) return opt_launch<T, 8, 2>(a, sink, what);
+  return opt_launch<T, 4, (sizeof(T) == 2 ? 2 : 4)>(a, sink, what);
+}
+
+template <typename Sink>
+static int opt_dispatch_dtype(int dtype, const OptArgs& a, const Sink& sink, const char* what) {
+  switch (dtype) {
+    case HSTU_DTYPE_BF16: return opt_dispatch<bf16_t>(a, sink, what);
+    case HSTU_DTYPE_F16: return opt_dispatch<f16_t>(a, sink, what);
+    default: return opt_dispatch<float>(a, sink, what);
+  }
 }
 
 }  // namespace hstu
@@ -344,10 +552,10 @@ int hstu_embedding_rowwise_adagrad_workspace_bytes(int64_t n, int32_t table_rows
   return HSTU_OK;
 }
 
-int hstu_embedding_rowwise_adagrad(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows, float* weight,
-                                   float* momentum1, float lr, float eps, void* workspace, int64_t workspace_bytes, int dtype,
-                                   void* stream) {
-  const char* what = "hstu_embedding_rowwise_adagrad";
+// the update behind both entry points; max_row_bytes: the widest dout row the entry point takes
+static int rowwise_adagrad_impl(const char* what, int max_row_bytes, const void* dout, const int32_t* idx, int64_t n, int32_t dim,
+                                int32_t table_rows, float* weight, float* momentum1, float lr, float eps, void* workspace,
+                                int64_t workspace_bytes, int dtype, void* stream) {
   if (!weight || !momentum1 || table_rows <= 0 || dim <= 0)
     return set_error(HSTU_EINVAL, "%s: weight and momentum1 must be non-NULL, sizes positive", what);
   if (!is_float_dtype(dtype)) return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32", what);
@@ -356,8 +564,8 @@ int hstu_embedding_rowwise_adagrad(const void* dout, const int32_t* idx, int64_t
     return set_error(HSTU_EUNSUPPORTED, "%s: rows of %d columns > %d", what, dim, kOptMaxDim);
   if ((dim * es) % 16 || ((uintptr_t)dout & 15) || ((uintptr_t)weight & 15))
     return set_error(HSTU_EINVAL, "%s: rows must be 16-byte multiples and 16-byte aligned", what);
-  if (dim * es > kOptMaxPieces * 64 * 16)
-    return set_error(HSTU_EUNSUPPORTED, "%s: rows of %d bytes > %d", what, dim * es, kOptMaxPieces * 64 * 16);
+  if (dim * es > max_row_bytes)
+    return set_error(HSTU_EUNSUPPORTED, "%s: rows of %d bytes > %d", what, dim * es, max_row_bytes);
   if (n < 0 || n > 0x7fffffffLL) return set_error(HSTU_EINVAL, "%s: n out of range", what);
   if (n == 0) return HSTU_OK;
   if (!dout || !idx || !workspace) return set_error(HSTU_EINVAL, "%s: NULL input", what);
@@ -373,12 +581,65 @@ int hstu_embedding_rowwise_adagrad(const void* dout, const int32_t* idx, int64_t
   size_t temp = l.temp_bytes;
   hipError_t e = sort_indices(ws + l.temp_off, temp, idx, sorted_idx, perm, n, table_rows, st);
   if (e != hipSuccess) return set_error(HSTU_ELAUNCH, "%s: sort failed: %s", what, hipGetErrorString(e));
-  const OptArgs a{dout, perm, sorted_idx, n, dim, weight, momentum1, partials, lr, eps, st};
-  switch (dtype) {
-    case HSTU_DTYPE_BF16: return opt_dispatch<bf16_t>(a, what);
-    case HSTU_DTYPE_F16: return opt_dispatch<f16_t>(a, what);
-    default: return opt_dispatch<float>(a, what);
+  const OptArgs a{dout, perm, sorted_idx, n, dim, partials, st};
+  return opt_dispatch_dtype(dtype, a, ApplySink{weight, momentum1, lr, eps}, what);
+}
+
+int hstu_embedding_rowwise_adagrad(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows, float* weight,
+                                   float* momentum1, float lr, float eps, void* workspace, int64_t workspace_bytes, int dtype,
+                                   void* stream) {
+  return rowwise_adagrad_impl("hstu_embedding_rowwise_adagrad", kOptMaxPieces * 64 * 16, dout, idx, n, dim, table_rows, weight, momentum1,
+                              lr, eps, workspace, workspace_bytes, dtype, stream);
+}
+
+int hstu_embedding_rowwise_adagrad_coalesced(const float* G, const int32_t* rows, int64_t n, int32_t dim, int32_t table_rows,
+                                             float* weight, float* momentum1, float lr, float eps, void* workspace,
+                                             int64_t workspace_bytes, void* stream) {
+  return rowwise_adagrad_impl("hstu_embedding_rowwise_adagrad_coalesced", kOptMaxDim * (int)sizeof(float), G, rows, n, dim, table_rows,
+                              weight, momentum1, lr, eps, workspace, workspace_bytes, HSTU_DTYPE_F32, stream);
+}
+
+int hstu_embedding_grad_coalesce_workspace_bytes(int64_t n, int32_t table_rows, int64_t* bytes) {
+  if (!bytes || n < 0 || n > 0x7fffffffLL || table_rows <= 0)
+    return set_error(HSTU_EINVAL, "hstu_embedding_grad_coalesce_workspace_bytes: bad arguments");
+  *bytes = (int64_t)coalesce_layout(n, table_rows).total;
+  return HSTU_OK;
+}
+
+int hstu_embedding_grad_coalesce(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows, float scale,
+                                 int32_t* rows, float* G, int32_t* count, void* workspace, int64_t workspace_bytes, int dtype,
+                                 void* stream) {
+  const char* what = "hstu_embedding_grad_coalesce";
+  if (!count || table_rows <= 0 || dim <= 0) return set_error(HSTU_EINVAL, "%s: count must be non-NULL, sizes positive", what);
+  if (!is_float_dtype(dtype)) return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32", what);
+  const int es = dtype_bytes(dtype);
+  if (dim > kOptMaxDim)                             // before any product with dim: dim * es must not wrap
+    return set_error(HSTU_EUNSUPPORTED, "%s: rows of %d columns > %d", what, dim, kOptMaxDim);
+  if ((dim * es) % 16 || ((uintptr_t)dout & 15) || ((uintptr_t)G & 15))
+    return set_error(HSTU_EINVAL, "%s: rows must be 16-byte multiples and 16-byte aligned", what);
+  if (dim * es > kOptMaxPieces * 64 * 16)
+    return set_error(HSTU_EUNSUPPORTED, "%s: rows of %d bytes > %d", what, dim * es, kOptMaxPieces * 64 * 16);
+  if (n < 0 || n > 0x7fffffffLL) return set_error(HSTU_EINVAL, "%s: n out of range", what);
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) {
+    hipError_t e = hipMemsetAsync(count, 0, sizeof(int32_t), st);
+    return e == hipSuccess ? HSTU_OK : set_error(HSTU_ELAUNCH, "%s: clearing count failed: %s", what, hipGetErrorString(e));
   }
+  if (!dout || !idx || !rows || !G || !workspace) return set_error(HSTU_EINVAL, "%s: NULL input", what);
+  const CoalesceLayout l = coalesce_layout(n, table_rows);
+  if (workspace_bytes < (int64_t)l.total || ((uintptr_t)workspace & 255))
+    return set_error(HSTU_EINVAL, "%s: workspace too small or not 256-byte aligned (hstu_embedding_grad_coalesce_workspace_bytes)", what);
+  char* ws = (char*)workspace;
+  int32_t* sorted_idx = (int32_t*)ws;
+  int32_t* perm = (int32_t*)(ws + l.opt.part);
+  float* partials = (float*)(ws + l.opt.partials_off);
+  int32_t* rank = (int32_t*)(ws + l.rank_off);
+  size_t temp = l.opt.temp_bytes;
+  hipError_t e = sort_indices(ws + l.opt.temp_off, temp, idx, sorted_idx, perm, n, table_rows, st);
+  if (e != hipSuccess) return set_error(HSTU_ELAUNCH, "%s: sort failed: %s", what, hipGetErrorString(e));
+  if (int rc = launch_head_ranks(sorted_idx, n, (int32_t*)(ws + l.tiles_off), rank, count, st, what)) return rc;
+  const OptArgs a{dout, perm, sorted_idx, n, dim, partials, st};
+  return opt_dispatch_dtype(dtype, a, EmitSink{rows, G, rank, scale}, what);
 }
 
 }  // extern "C"

@@ -197,8 +197,10 @@ class EmbeddingCollection(torch.nn.Module):
         return rows_of
 
     def apply_rowwise_adagrad_in_backward(self, lr: float, eps: float = 1e-8, weight_decay: float = 0.0,
-                                          rows_dtype: Optional[torch.dtype] = None, tables: Optional[List[str]] = None) -> None:
-        apply_rowwise_adagrad_in_backward(self, lr, eps=eps, weight_decay=weight_decay, rows_dtype=rows_dtype, tables=tables)
+                                          rows_dtype: Optional[torch.dtype] = None, tables: Optional[List[str]] = None,
+                                          replicated: bool = False, process_group: Any = None, average: bool = True) -> None:
+        apply_rowwise_adagrad_in_backward(self, lr, eps=eps, weight_decay=weight_decay, rows_dtype=rows_dtype, tables=tables,
+                                          replicated=replicated, process_group=process_group, average=average)
 
     def set_learning_rate(self, lr: float) -> None:
         for cfg in self._fused.values():
@@ -221,14 +223,22 @@ def _momentum1_name(table: str) -> str:
 
 
 def apply_rowwise_adagrad_in_backward(collection: Any, lr: float, eps: float = 1e-8, weight_decay: float = 0.0,
-                                      rows_dtype: Optional[torch.dtype] = None, tables: Optional[List[str]] = None) -> None:
+                                      rows_dtype: Optional[torch.dtype] = None, tables: Optional[List[str]] = None,
+                                      replicated: bool = False, process_group: Any = None, average: bool = True) -> None:
     """Train the named tables of an ``EmbeddingCollection`` (default: all; a ``DlrmHSTU`` stands for its collection) with
     row-wise Adagrad applied in backward -- what ``apply_optimizer_in_backward(RowWiseAdagrad, ...)`` does to the reference's
     TorchRec modules (dlrm_v3/train/utils.py:190-227).  Afterwards the forward issues one gather per table, backward updates
     the touched rows in place (ops/embedding.py) and leaves ``weight.grad`` None, so a dense optimizer over
     ``model.parameters()`` skips these tables.  ``lr``, ``eps`` and ``rows_dtype`` are kept per table: a later call that names
     other tables leaves the earlier ones as they were.  The state is one fp32 ``momentum1`` per table row, a non-persistent buffer
-    (the module's state_dict keeps TorchRec's keys; see ``fused_optimizer_state_dict``)."""
+    (the module's state_dict keeps TorchRec's keys; see ``fused_optimizer_state_dict``).
+
+    ``replicated=True``: data-parallel training with a copy of the table on every rank of ``process_group`` (None: the default
+    group).  Backward then applies the row gradients of ALL ranks -- their mean with ``average`` (what ``GradientAllReducer``
+    does to the dense gradients), else their sum -- in rank order on every rank, so the copies keep equal bits
+    (ops/embedding.py).  PRECONDITION: the copies start identical (``ops.embedding.broadcast_fused_tables``) and every rank calls
+    backward for the same tables in the same order.  Off by default: without it more than one rank is refused.  The three
+    settings are kept per table like ``lr``."""
     collection = getattr(collection, "_embedding_collection", collection)
     if weight_decay != 0.0:
         raise NotImplementedError(f"weight_decay = {weight_decay}: TorchRec's RowWiseAdagrad and fbgemm's exact row-wise Adagrad "
@@ -246,11 +256,12 @@ def apply_rowwise_adagrad_in_backward(collection: Any, lr: float, eps: float = 1
         if table in collection._fused:
             cfg = collection._fused[table]               # named again: this call's settings replace the table's
             cfg.lr, cfg.eps, cfg.rows_dtype = float(lr), float(eps), rows_dtype
+            cfg.replicated, cfg.process_group, cfg.average = bool(replicated), process_group, bool(average)
             continue
         weight = collection.embeddings[table].weight
         collection.register_buffer(_momentum1_name(table), torch.zeros(weight.shape[0], dtype=torch.float32, device=weight.device),
                                    persistent=False)
-        collection._fused[table] = RowWiseAdagradConfig(lr, eps, rows_dtype)
+        collection._fused[table] = RowWiseAdagradConfig(lr, eps, rows_dtype, replicated, process_group, average)
 
 
 def _get_supervision_labels_and_weights(

@@ -7,10 +7,18 @@ Adagrad with ``weight_decay = 0`` and ``lr_decay = 0``).  For every table row r 
     W[r, :]      = W[r, :] - lr / (sqrt(momentum1[r]) + eps) * G[r, :]              (the updated momentum1)
 
 One HIP pass (csrc/embedding_optim.hip) that reads the gradient rows and touches only those table rows: no table-sized
-gradient exists at any point."""
+gradient exists at any point.
+
+Data-parallel ranks that each hold a copy of a table (``RowWiseAdagradConfig.replicated``) keep the copies bit-identical
+without ever broadcasting them: every rank coalesces its batch to one fp32 row per distinct id
+(``coalesce_row_gradients``), the ranks all-gather those short lists (``exchange_row_gradients``), and every rank applies
+the same update to the same concatenation in rank order.  The update is deterministic and its summation order depends
+only on that list, so equal inputs give equal bits.  PRECONDITION: the copies start identical
+(``broadcast_fused_tables``) and every rank runs backward for the same tables in the same order -- the collectives pair
+up by issue order.  ``assert_fused_tables_in_sync`` checks the outcome."""
 
 import ctypes as C
-from typing import Any, Optional
+from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
@@ -19,18 +27,25 @@ from generative_recommenders_amd import _lib as L
 
 class RowWiseAdagradConfig:
     """step size, epsilon and the dtype of the gathered rows (None: the table's) of one fused table; mutable, read at every
-    forward / backward (``set_learning_rate``)"""
+    forward / backward (``set_learning_rate``).  ``replicated``: every rank of ``process_group`` (None: the default group)
+    holds a copy of the table and backward applies all ranks' row gradients to it, averaged over the ranks (``average``,
+    the ``GradientAllReducer`` default) or summed; off by default."""
 
-    def __init__(self, lr: float, eps: float = 1e-8, rows_dtype: Optional[torch.dtype] = None) -> None:
+    def __init__(self, lr: float, eps: float = 1e-8, rows_dtype: Optional[torch.dtype] = None, replicated: bool = False,
+                 process_group: Any = None, average: bool = True) -> None:
         self.lr = float(lr)
         self.eps = float(eps)
         self.rows_dtype = rows_dtype
+        self.replicated = bool(replicated)
+        self.process_group = process_group
+        self.average = bool(average)
 
 
 def rowwise_adagrad_update_(weight: torch.Tensor, momentum1: torch.Tensor, idx: torch.Tensor, dout: torch.Tensor, lr: float,
                             eps: float = 1e-8) -> None:
     """in place: the update above on ``weight`` (rows, dim) fp32 and ``momentum1`` (rows) fp32 for the ids ``idx`` (n) and
-    their gradient rows ``dout`` (n, dim) in bf16, fp16 or fp32.  Ids outside [0, rows) are the caller's error (not checked)."""
+    their gradient rows ``dout`` (n, dim) in bf16, fp16 or fp32.  Ids outside [0, rows) are the caller's error (not checked).
+    fp32 rows of more than 1024 columns (the coalesced lists of wide tables) go through ``hstu_embedding_rowwise_adagrad_coalesced``."""
     for name, t in (("weight", weight), ("momentum1", momentum1), ("idx", idx), ("dout", dout)):
         L.require_gpu_tensor(t, name)
     if not (weight.device == momentum1.device == idx.device == dout.device):
@@ -56,9 +71,121 @@ def rowwise_adagrad_update_(weight: torch.Tensor, momentum1: torch.Tensor, idx: 
     L.check(L.lib().hstu_embedding_rowwise_adagrad_workspace_bytes(n, rows, C.byref(need)))
     ws = torch.empty(max(need.value, 256), dtype=torch.uint8, device=weight.device)
     with torch.cuda.device(weight.device):
+        if dout.dtype == torch.float32 and dim > 1024:      # fp32 rows above 4 KiB: the coalesced lists of wide tables
+            L.check(L.lib().hstu_embedding_rowwise_adagrad_coalesced(
+                dout.data_ptr(), idx.data_ptr(), n, dim, rows, weight.data_ptr(), momentum1.data_ptr(), float(lr), float(eps),
+                ws.data_ptr(), ws.numel(), L.current_stream_ptr(weight.device)))
+            return
         L.check(L.lib().hstu_embedding_rowwise_adagrad(
             dout.data_ptr(), idx.data_ptr(), n, dim, rows, weight.data_ptr(), momentum1.data_ptr(), float(lr), float(eps),
             ws.data_ptr(), ws.numel(), L.torch_dtype_code(dout.dtype), L.current_stream_ptr(weight.device)))
+
+
+def coalesce_row_gradients(idx: torch.Tensor, dout: torch.Tensor, table_rows: int,
+                           scale: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``(rows, G, count)``: the distinct ids of ``idx`` (n) in ascending order, ``G[s] = scale * (sum of the dout rows whose id
+    is rows[s])`` in fp32 -- the sum ``rowwise_adagrad_update_`` forms for the same ``(idx, dout)``, addition for addition, the
+    multiply applied once at the end -- and their number, one int32 on the device.  ``rows`` (n) int32 and ``G`` (n, dim) fp32
+    are the capacity-n buffers; only the first ``count`` entries are defined.  No synchronisation happens here: the caller
+    reads ``count`` when it needs it (csrc/embedding_optim.hip, ``hstu_embedding_grad_coalesce``)."""
+    L.require_gpu_tensor(idx, "idx")
+    L.require_gpu_tensor(dout, "dout")
+    if idx.device != dout.device:
+        raise RuntimeError(f"coalesce_row_gradients: idx and dout must be on one device, got {idx.device} and {dout.device}")
+    if dout.dim() != 2 or idx.dim() != 1 or idx.shape[0] != dout.shape[0]:
+        raise RuntimeError(f"coalesce_row_gradients: idx (n) and dout (n, dim), got {tuple(idx.shape)} and {tuple(dout.shape)}")
+    n, dim = dout.shape
+    dout = dout.detach().contiguous()
+    idx = idx.detach().to(torch.int32).contiguous()
+    rows = torch.empty(n, dtype=torch.int32, device=dout.device)
+    G = torch.empty((n, dim), dtype=torch.float32, device=dout.device)
+    count = torch.empty(1, dtype=torch.int32, device=dout.device)
+    need = C.c_int64(0)
+    L.check(L.lib().hstu_embedding_grad_coalesce_workspace_bytes(n, int(table_rows), C.byref(need)))
+    ws = torch.empty(max(need.value, 256), dtype=torch.uint8, device=dout.device)
+    with torch.cuda.device(dout.device):
+        L.check(L.lib().hstu_embedding_grad_coalesce(
+            dout.data_ptr(), idx.data_ptr(), n, dim, int(table_rows), float(scale), rows.data_ptr(), G.data_ptr(), count.data_ptr(),
+            ws.data_ptr(), ws.numel(), L.torch_dtype_code(dout.dtype), L.current_stream_ptr(dout.device)))
+    return rows, G, count
+
+
+def exchange_row_gradients(rows: torch.Tensor, G: torch.Tensor, count: torch.Tensor,
+                           group: Any = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """All ranks' coalesced lists, concatenated IN RANK ORDER with the padding stripped: ``(rows_all, G_all)``, the same on
+    every rank of ``group``.  The counts are all-gathered first and read on the host -- the one synchronisation --, then
+    ``rows`` and ``G`` travel padded to the largest count.  On ``nccl`` the collectives run on device buffers; any other
+    backend (``gloo``, the rehearsal backend of ``data_parallel.init_from_env``) stages them through host memory."""
+    dist = torch.distributed
+    world, me = dist.get_world_size(group), dist.get_rank(group)
+    dev = rows.device
+    via = dev if dist.get_backend(group) == "nccl" else torch.device("cpu")
+    counts_t = [torch.empty(1, dtype=torch.int32, device=via) for _ in range(world)]
+    dist.all_gather(counts_t, count.reshape(1).to(device=via, dtype=torch.int32), group=group)
+    counts: List[int] = torch.cat(counts_t).cpu().tolist()
+    cap, mine = max(counts), counts[me]
+    if cap == 0:
+        return rows[:0], G[:0]
+
+    def gathered(t: torch.Tensor) -> torch.Tensor:
+        send = torch.zeros((cap,) + tuple(t.shape[1:]), dtype=t.dtype, device=via)
+        send[:mine].copy_(t[:mine])
+        recv = [torch.empty_like(send) for _ in range(world)]
+        dist.all_gather(recv, send, group=group)
+        return torch.cat([r[:c] for r, c in zip(recv, counts)]).to(dev)
+
+    return gathered(rows), gathered(G)
+
+
+def _fused_tables(collection: Any) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
+    """table name -> (weight, momentum1) of the tables an ``EmbeddingCollection`` (or the model that holds one) trains in backward"""
+    collection = getattr(collection, "_embedding_collection", collection)
+    state = collection.fused_optimizer_state_dict()
+    return {t: (collection.embeddings[t].weight.detach(), state[f"{t}.momentum1"].detach()) for t in collection._fused}
+
+
+def fused_tables_checksum(collection: Any) -> Dict[str, int]:
+    """Per fused table one exact integer: the wrapping int64 sum of the fp32 bit patterns (read as int32) of ``weight`` and of
+    ``momentum1``.  Equal tables give equal sums; one flipped bit changes the sum."""
+    bits = lambda t: int(t.contiguous().view(torch.int32).sum(dtype=torch.int64))
+    wrap = lambda v: (v + (1 << 63)) % (1 << 64) - (1 << 63)
+    return {t: wrap(bits(w) + bits(m)) for t, (w, m) in _fused_tables(collection).items()}
+
+
+def assert_fused_tables_in_sync(collection: Any, group: Any = None) -> None:
+    """Raise when the ranks of ``group`` hold different fused tables or states (``fused_tables_checksum``, all-gathered).
+    A collective: every rank calls it.  Without a process group there is nothing to compare."""
+    dist = torch.distributed
+    if not (dist.is_available() and dist.is_initialized()):
+        return
+    sums = fused_tables_checksum(collection)
+    if not sums:
+        return
+    tables = _fused_tables(collection)
+    dev = next(iter(tables.values()))[0].device if dist.get_backend(group) == "nccl" else torch.device("cpu")
+    mine = torch.tensor([sums[t] for t in tables], dtype=torch.int64, device=dev)
+    every = [torch.empty_like(mine) for _ in range(dist.get_world_size(group))]
+    dist.all_gather(every, mine, group=group)
+    every = torch.stack(every).cpu()
+    bad = [t for i, t in enumerate(tables) if not bool((every[:, i] == every[0, i]).all())]
+    if bad:
+        raise RuntimeError(f"fused tables differ between ranks: {bad} (checksums per rank: "
+                           f"{ {t: every[:, list(tables).index(t)].tolist() for t in bad} }).  Replicated tables stay equal only when "
+                           "they start equal (broadcast_fused_tables) and every rank runs backward for the same tables in the same order")
+
+
+def broadcast_fused_tables(collection: Any, src: int = 0, group: Any = None) -> None:
+    """Step 0 of replicated training: every rank's fused tables and their ``momentum1`` become rank ``src``'s (a collective;
+    staged through host memory on backends other than ``nccl``)."""
+    dist = torch.distributed
+    on_device = dist.get_backend(group) == "nccl"
+    with torch.no_grad():
+        for weight, momentum1 in _fused_tables(collection).values():
+            for t in (weight, momentum1):
+                buf = t if on_device else t.cpu()
+                dist.broadcast(buf, src=src, group=group)
+                if buf is not t:
+                    t.copy_(buf)
 
 
 def _refuse_replicated_tables() -> None:
@@ -81,6 +208,17 @@ class _GatherRowsFusedFunction(torch.autograd.Function):
     def backward(ctx, g):
         (idx,) = ctx.saved_tensors
         weight, momentum1, cfg = ctx.table
+        dist = torch.distributed
+        if getattr(cfg, "replicated", False) and dist.is_available() and dist.is_initialized():
+            # every rank applies every rank's row gradients, in rank order: the copies of the table keep equal bits.  The
+            # update's stable sort puts a row's up-to-world partial sums in rank order on every rank.
+            group = cfg.process_group
+            scale = 1.0 / dist.get_world_size(group) if cfg.average else 1.0
+            with torch.no_grad():
+                rows, G, count = coalesce_row_gradients(idx, g, weight.shape[0], scale)
+                rows_all, G_all = exchange_row_gradients(rows, G, count, group)
+                rowwise_adagrad_update_(weight, momentum1, rows_all, G_all, cfg.lr, cfg.eps)
+            return None, None, None, None, None
         _refuse_replicated_tables()
         with torch.no_grad():
             rowwise_adagrad_update_(weight, momentum1, idx, g, cfg.lr, cfg.eps)

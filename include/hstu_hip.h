@@ -423,6 +423,29 @@ int hstu_embedding_rowwise_adagrad_workspace_bytes(int64_t n, int32_t table_rows
 int hstu_embedding_rowwise_adagrad(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows,
                                    float* weight, float* momentum1, float lr, float eps, void* workspace,
                                    int64_t workspace_bytes, int dtype, void* stream);
+/* The same update for fp32 gradient rows of up to 2048 columns (8 KiB), the rows hstu_embedding_grad_coalesce writes: G (n, dim)
+ * fp32, rows (n) the ids (duplicates are summed in list order, as above).  Everything else, the workspace query included, is
+ * hstu_embedding_rowwise_adagrad's with dtype fp32.  The sum of squares of G[r, :] is added in one tree whatever the row
+ * layout, so coalescing 16-bit rows and applying them here gives the bits of the one-shot update on the 16-bit rows. */
+int hstu_embedding_rowwise_adagrad_coalesced(const float* G, const int32_t* rows, int64_t n, int32_t dim, int32_t table_rows,
+                                             float* weight, float* momentum1, float lr, float eps, void* workspace,
+                                             int64_t workspace_bytes, void* stream);
+/* The first half of that update alone, for data-parallel ranks that exchange their row gradients before applying them:
+ * the batch's (idx, dout) coalesced to one fp32 row per distinct id.
+ *   rows[s]  = the s-th smallest distinct id of idx (ascending), s < u = *count
+ *   G[s, :]  = scale * (sum over e with idx[e] == rows[s] of dout[e, :])   (fp32; the sum is hstu_embedding_rowwise_adagrad's
+ *              for the same (idx, dout, dim, dtype), addition for addition; the multiply is applied once, last)
+ *   *count   = u, one int32 in device memory
+ * rows (n) int32 and G (n, dim) fp32 have room for n entries; only the first u are written, the rest keeps its bits.
+ * n == 0 writes *count = 0 and nothing else.  Same limits and guarantees as the update: dim <= 2048, dout rows 16-byte
+ * multiples of at most 4 KiB, dout and G 16-byte aligned, n <= 2^31 - 1, 0 <= idx[e] < table_rows not checked; no float
+ * atomics, no host synchronisation, bit-identical from run to run.  `workspace`: device memory, 256-byte aligned, at least
+ * hstu_embedding_grad_coalesce_workspace_bytes(n, table_rows) bytes: the update's plus 4 bytes per id for the segments'
+ * slots (a scan over the segment-head flags of the sorted ids) -- O(n), independent of table_rows and dim. */
+int hstu_embedding_grad_coalesce_workspace_bytes(int64_t n, int32_t table_rows, int64_t* bytes);
+int hstu_embedding_grad_coalesce(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows, float scale,
+                                 int32_t* rows, float* G, int32_t* count, void* workspace, int64_t workspace_bytes, int dtype,
+                                 void* stream);
 
 /* ---- output postprocessor: row L2 normalisation ---------------------------------------------------------
  * y = x / max(||x||_2, eps) per row of (rows, dim), and its backward.  Replaces L2NormPostprocessor.forward

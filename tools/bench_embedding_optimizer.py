@@ -13,7 +13,15 @@ no amount of work.  Bytes are algorithmic: n * dim * sizeof(dout) + unique * (2 
 once, every touched table row and its state read and written once; GB/s is those bytes over the time, share_of_8TBs the
 same over 8 TB/s.
 
+--replicated W times the data-parallel path for tables replicated on W ranks instead, the ranks emulated on the one GPU: the
+batch is cut into W equal shards, every shard is coalesced to one fp32 row per distinct id with scale 1 / W
+(``coalesce_row_gradients``), the W lists are concatenated in rank order and applied with the same update.  What one rank
+does per step -- coalesce ITS shard, then the merged update -- is timed against the one-shot update of the whole batch and of
+one shard, all in one process, alternating.  ``sent_bytes`` is what a rank puts on the wire, u * (4 + 4 * dim) for its u
+distinct ids, beside the raw alternative n / W * (4 + es * dim); the exchange itself is not timed (one GPU).
+
     python tools/bench_embedding_optimizer.py [--iters 10] [--rounds 7] [--out profiles/r15_bench_embedding_optimizer.json]
+    python tools/bench_embedding_optimizer.py --replicated 8 --out profiles/r17_bench_embedding_replicated.json
 """
 import argparse
 import json
@@ -25,7 +33,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from generative_recommenders_amd.ops.embedding import rowwise_adagrad_update_  # noqa: E402
+from generative_recommenders_amd.ops.embedding import coalesce_row_gradients, rowwise_adagrad_update_  # noqa: E402
 from generative_recommenders_amd.ops.position import _table_grad  # noqa: E402
 
 DEV = "cuda"
@@ -99,18 +107,60 @@ def run(rows, n, dense, iters, rounds):
     return res
 
 
+def run_replicated(rows, n, world, iters, rounds):
+    g = torch.Generator(device=DEV).manual_seed(0)
+    idx32 = _zipf_ids(rows, n, g).to(torch.int32)
+    dout = (0.01 * torch.randn(n, DIM, device=DEV, generator=g)).to(torch.bfloat16)
+    weight = torch.randn(rows, DIM, device=DEV, generator=g)
+    momentum1 = torch.zeros(rows, device=DEV)
+    per = (n + world - 1) // world
+    shards = [(idx32[r * per:(r + 1) * per], dout[r * per:(r + 1) * per]) for r in range(world)]
+    lists = []
+    for i, d in shards:
+        r, G, count = coalesce_row_gradients(i, d, rows, 1.0 / world)
+        u = int(count)
+        lists.append((r[:u], G[:u]))
+    rows_all, G_all = torch.cat([l[0] for l in lists]), torch.cat([l[1] for l in lists])
+    i0, d0 = shards[0]
+    paths = {"one_shot_whole_batch": lambda: rowwise_adagrad_update_(weight, momentum1, idx32, dout, LR, EPS),
+             "one_shot_one_shard": lambda: rowwise_adagrad_update_(weight, momentum1, i0, d0, LR, EPS),
+             "coalesce_one_shard": lambda: coalesce_row_gradients(i0, d0, rows, 1.0 / world),
+             "merged_update": lambda: rowwise_adagrad_update_(weight, momentum1, rows_all, G_all, LR, EPS)}
+    for fn in paths.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in paths}
+    for _ in range(rounds):
+        for name, fn in paths.items():
+            times[name].append(_events_ms(fn, iters))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    u0, es = int(lists[0][0].numel()), dout.element_size()
+    return {"shape": {"table_rows": rows, "dim": DIM, "n": n, "world": world, "shard_n": int(i0.numel()), "shard_unique_ids": u0,
+                      "merged_rows": int(rows_all.numel()), "unique_ids": int(torch.unique(idx32).numel()), "dout": "bfloat16"},
+            "us": {k: round(1e3 * v, 2) for k, v in med.items()},
+            "us_rounds": {k: [round(1e3 * x, 2) for x in v] for k, v in times.items()},
+            "rank_step_over_one_shot_whole_batch": round((med["coalesce_one_shard"] + med["merged_update"]) / med["one_shot_whole_batch"], 3),
+            "rank_step_over_one_shot_one_shard": round((med["coalesce_one_shard"] + med["merged_update"]) / med["one_shot_one_shard"], 3),
+            "sent_bytes": {"coalesced": u0 * (4 + 4 * DIM), "raw": int(i0.numel()) * (4 + es * DIM)}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--out", default=None)
+    ap.add_argument("--replicated", type=int, default=0, metavar="W", help="time the replicated-table path with W emulated ranks")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_embedding_optimizer: needs a GPU (a timing without one says nothing)")
     res = {"device": torch.cuda.get_device_name(0), "iters": args.iters, "rounds": args.rounds, "workloads": {}}
     for name in args.shapes.split(","):
-        res["workloads"][name] = run(*SHAPES[name], args.iters, args.rounds)
+        if args.replicated > 0:
+            res["workloads"][name] = run_replicated(*SHAPES[name][:2], args.replicated, args.iters, args.rounds)
+        else:
+            res["workloads"][name] = run(*SHAPES[name], args.iters, args.rounds)
         torch.cuda.empty_cache()
     text = json.dumps(res)
     if args.out:
