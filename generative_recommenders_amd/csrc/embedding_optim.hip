@@ -28,9 +28,17 @@
 // applied to the table but written out, scale * G[r, :] and r, at the segment's rank among the segment heads -- the short
 // list a data-parallel rank exchanges (ops/embedding.py).  The rank comes from an inclusive scan over the head flags of the
 // sorted positions (three small kernels in front of the chunk kernel); the sums are the update's, addition for addition.
+//
+// A table stored in 16 bits (fp16 / bf16; hstu_embedding_rowwise_adagrad_lowp) is a second element type of the same
+// kernels (ApplySink16): its prefetched rows stay in their raw 16-bit form, half the registers, until the segment ends;
+// there the row is widened to fp32, updated by apply_update's arithmetic -- the fp32 result equals the fp32 table's bit for
+// bit -- and written back through the stochastic rounding of stochastic_round.h, whose random bits are a function of
+// (seed, table row, column) alone.  momentum1 stays fp32.
 #include "hstu_common.cuh"
 #include "capi_internal.h"
 #include "embedding_sort.cuh"
+#include "row_pass.cuh"
+#include "stochastic_round.h"
 
 namespace hstu {
 
@@ -143,13 +151,25 @@ __device__ __forceinline__ void apply_update(const float (&acc)[NP][VEC], float 
 // What the chunk and combine kernels do with a finished segment: apply it to the table (the update) ...
 struct ApplySink {
   static constexpr bool kApply = true;
+  typedef float WT;
   float *weight, *momentum1;
   float lr, eps;
+};
+// ... to a table of 16-bit rows (W: f16_t or bf16_t), written back by stochastic rounding ...
+template <typename W>
+struct ApplySink16 {
+  static constexpr bool kApply = true;
+  typedef W WT;
+  W* weight;
+  float* momentum1;
+  float lr, eps;
+  uint64_t seed;
 };
 // ... or write it out (the coalesce): rank[p] = number of segment heads among the sorted positions 0 .. p, the same for
 // every position of a segment, so any of them names the segment's slot rank[p] - 1
 struct EmitSink {
   static constexpr bool kApply = false;
+  typedef float WT;
   int32_t* rows;
   float* G;
   const int32_t* rank;
@@ -165,6 +185,120 @@ __device__ __forceinline__ void emit_segment(const float (&acc)[NP][VEC], int la
     for (int c = 0; c < VEC; ++c) out[j][c] = s.scale * acc[j][c];
   store_f32_row<VEC, NP>(s.G + (int64_t)slot * dim, lane, pieces, out);
   if (lane == 0) s.rows[slot] = id;
+}
+
+// The registers a prefetched table row waits in: fp32 as loaded, or the raw 16-bit elements, two per register (VEC / 2
+// registers per piece: 16 bytes per lane and piece next to 16-bit gradient rows, 8 bytes next to fp32 ones)
+template <typename WT, int VEC, int NP>
+struct WRow { typedef float type[NP][VEC]; };
+template <int VEC, int NP>
+struct WRow<f16_t, VEC, NP> { typedef uint32_t type[NP][VEC / 2]; };
+template <int VEC, int NP>
+struct WRow<bf16_t, VEC, NP> { typedef uint32_t type[NP][VEC / 2]; };
+
+template <int VEC, int NP>
+__device__ __forceinline__ void load_w_row(const float* __restrict__ row, int lane, int pieces, float (&w)[NP][VEC]) {
+  load_f32_row<VEC, NP>(row, lane, pieces, w);
+}
+template <int VEC, int NP, typename W>
+__device__ __forceinline__ void load_w_row(const W* __restrict__ row, int lane, int pieces, uint32_t (&w)[NP][VEC / 2]) {
+  static_assert(sizeof(W) == 2, "16-bit table rows");
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    const int p = lane + 64 * j;
+    if (p < pieces) {
+      if constexpr (VEC == 8) *(u32x4*)&w[j][0] = *(const u32x4*)(row + (int64_t)p * VEC);
+      else *(u32x2*)&w[j][0] = *(const u32x2*)(row + (int64_t)p * VEC);
+    }
+  }
+}
+
+// 16 raw bits of a table element -> fp32, and the stochastic rounding back (stochastic_round.h)
+template <typename W>
+__device__ __forceinline__ float widen16(uint32_t h) {
+  if constexpr (__is_same(W, bf16_t)) return __builtin_bit_cast(float, h << 16);
+  else return (float)__builtin_bit_cast(f16_t, (uint16_t)h);
+}
+template <typename W>
+__device__ __forceinline__ uint32_t round16(float x, uint32_t r) {
+  if constexpr (__is_same(W, bf16_t)) return hstu_sr_bf16(__builtin_bit_cast(uint32_t, x), r);
+  else return hstu_sr_f16(__builtin_bit_cast(uint32_t, x), r);
+}
+// The rule has a PLAIN form wherever it needs none of its special cases: finite values that cannot reach the clamp (bf16),
+// finite values of at least 2^-14 (fp16).  There bf16 is the upper half of bits + r, and fp16 is bits + 13 random bits with
+// the low 13 cleared -- a value ON the fp16 grid, so the hardware's conversion is exact whatever its rounding mode --,
+// clamped to +-65504 as a float.  Same bits as round16 (tests/test_embedding_lowp_gpu.py holds both forms against the numpy
+// restatement), a fifth of the instructions: the update is bound by them, not by bytes, at the reference's row width.
+template <typename W>
+__device__ __forceinline__ bool is_plain16(float x) {
+  if constexpr (__is_same(W, bf16_t)) return fabsf(x) <= __builtin_bit_cast(float, 0x7f7f0000u);     // false for NaN
+  else return fabsf(x) >= 0x1p-14f && fabsf(x) < __builtin_inff();
+}
+// (lo, hi) with the 32 random bits h of their column pair -> the two 16-bit results, packed as they lie in memory
+template <typename W>
+__device__ __forceinline__ uint32_t round_pair_plain(float lo, float hi, uint32_t h) {
+  const uint32_t a = __builtin_bit_cast(uint32_t, lo), b = __builtin_bit_cast(uint32_t, hi);
+  if constexpr (__is_same(W, bf16_t)) {
+    return ((a + (h & 0xffffu)) >> 16) | ((b + (h >> 16)) & 0xffff0000u);
+  } else {
+    const float x = __builtin_bit_cast(float, (a + (h & 0x1fffu)) & ~0x1fffu);
+    const float y = __builtin_bit_cast(float, (b + ((h >> 16) & 0x1fffu)) & ~0x1fffu);
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(fminf(fmaxf(x, -65504.f), 65504.f), fminf(fmaxf(y, -65504.f), 65504.f)));
+  }
+}
+// VEC fp32 values of table row `row` from column pair `pair0` on -> VEC / 2 registers of 16-bit results.  The plain form
+// when every value of every lane of the wave allows it (one branch per wave and piece, no divergence), else the rule in full.
+template <typename W, int VEC>
+__device__ __forceinline__ void round_piece(const float (&x)[VEC], uint64_t seed, uint32_t row, uint32_t pair0, uint32_t (&out)[VEC / 2]) {
+  uint32_t h[VEC / 2];
+  bool plain = true;
+#pragma unroll
+  for (int c = 0; c < VEC / 2; ++c) {
+    h[c] = hstu_sr_hash(seed, row, pair0 + c);
+    plain = plain && is_plain16<W>(x[2 * c]) && is_plain16<W>(x[2 * c + 1]);
+  }
+  if (__builtin_amdgcn_ballot_w64(!plain) == 0) {
+#pragma unroll
+    for (int c = 0; c < VEC / 2; ++c) out[c] = round_pair_plain<W>(x[2 * c], x[2 * c + 1], h[c]);
+  } else {
+#pragma unroll
+    for (int c = 0; c < VEC / 2; ++c) out[c] = round16<W>(x[2 * c], h[c] & 0xffffu) | (round16<W>(x[2 * c + 1], h[c] >> 16) << 16);
+  }
+}
+
+// the finished segment of table row `id` applied to the table: the fp32 table's update as it is ...
+template <int VEC, int NP>
+__device__ __forceinline__ void finish_apply(const float (&acc)[NP][VEC], float (&w)[NP][VEC], float m_old, int lane, int pieces, int dim,
+                                             int id, const ApplySink& s) {
+  apply_update<VEC, NP>(acc, w, m_old, lane, pieces, dim, s.weight + (int64_t)id * dim, s.momentum1 + id, s.lr, s.eps);
+}
+// ... and the 16-bit table's: apply_update's arithmetic on the widened row (the multiply-add contracted as the compiler
+// contracts it there, pinned by fmaf), every element then rounded with its own 16 random bits -- one hash per column pair
+// (round_piece)
+template <int VEC, int NP, typename W>
+__device__ __forceinline__ void finish_apply(const float (&acc)[NP][VEC], const uint32_t (&raw)[NP][VEC / 2], float m_old, int lane, int pieces,
+                                             int dim, int id, const ApplySink16<W>& s) {
+  const float ss = row_sum_of_squares<VEC, NP>(acc, lane, pieces);
+  const float m_new = m_old + ss / (float)dim;
+  const float step = s.lr / (sqrtf(m_new) + s.eps);
+  W* __restrict__ w_row = s.weight + (int64_t)id * dim;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    const int p = lane + 64 * j;
+    if (p < pieces) {
+      float x[VEC];
+      uint32_t out[VEC / 2];
+#pragma unroll
+      for (int c = 0; c < VEC / 2; ++c) {
+        x[2 * c] = fmaf(-step, acc[j][2 * c], widen16<W>(raw[j][c] & 0xffffu));
+        x[2 * c + 1] = fmaf(-step, acc[j][2 * c + 1], widen16<W>(raw[j][c] >> 16));
+      }
+      round_piece<W, VEC>(x, s.seed, (uint32_t)id, (uint32_t)(p * (VEC / 2)), out);
+      if constexpr (VEC == 8) *(u32x4*)(w_row + (int64_t)p * VEC) = *(const u32x4*)&out[0];
+      else *(u32x2*)(w_row + (int64_t)p * VEC) = *(const u32x2*)&out[0];
+    }
+  }
+  if (lane == 0) s.momentum1[id] = m_new;
 }
 
 template <typename T, int NP, int U, int kChunk, typename Sink>
@@ -201,7 +335,8 @@ __global__ __launch_bounds__(kOptWaves * 64) void adagrad_chunk_kernel(const T* 
       for (int c = 0; c < VEC; ++c) acc[j][c] = 0.f;
     for (int r0 = 0; r0 < cnt; r0 += U) {
       u32x4 v[U][NP];
-      float w[U][NP][VEC], m_old[U];
+      typename WRow<typename Sink::WT, VEC, NP>::type w[U];
+      float m_old[U];
       int id[U], slot[U];
       bool ends[U], whole[U];
       bool began_before = open_left;                // of the segment that row u belongs to
@@ -224,7 +359,7 @@ __global__ __launch_bounds__(kOptWaves * 64) void adagrad_chunk_kernel(const T* 
         slot[u] = 0;
         if constexpr (Sink::kApply) {
           if (whole[u]) {                           // the table row travels with the gradient rows
-            load_f32_row<VEC, NP>(sink.weight + (int64_t)id[u] * dim, lane, pieces, w[u]);
+            load_w_row<VEC, NP>(sink.weight + (int64_t)id[u] * dim, lane, pieces, w[u]);
             m_old[u] = sink.momentum1[id[u]];
           }
         } else {
@@ -245,8 +380,7 @@ __global__ __launch_bounds__(kOptWaves * 64) void adagrad_chunk_kernel(const T* 
         if (ends[u]) {
           if (whole[u]) {
             if constexpr (Sink::kApply)
-              apply_update<VEC, NP>(acc, w[u], m_old[u], lane, pieces, dim, sink.weight + (int64_t)id[u] * dim, sink.momentum1 + id[u],
-                                    sink.lr, sink.eps);
+              finish_apply<VEC, NP>(acc, w[u], m_old[u], lane, pieces, dim, id[u], sink);
             else
               emit_segment<VEC, NP>(acc, lane, pieces, dim, sink, id[u], slot[u]);
           } else {
@@ -296,12 +430,13 @@ __global__ __launch_bounds__(kCombineWaves * 64) void adagrad_combine_kernel(con
     const int64_t total = last - b + 1;                      // list item 0: slot (b, 1); item i > 0: slot (b + i, 0)
     const int64_t share = (total + kCombineWaves - 1) / kCombineWaves;
     const int64_t i0 = wave * share, i1 = min(total, i0 + share);
-    float w[NP][VEC], acc[NP][VEC];
+    typename WRow<typename Sink::WT, VEC, NP>::type w;
+    float acc[NP][VEC];
     float m_old = 0.f;
     int slot = 0;
     if (wave == 0) {
       if constexpr (Sink::kApply) {
-        load_f32_row<VEC, NP>(sink.weight + (int64_t)id * dim, lane, pieces, w);
+        load_w_row<VEC, NP>(sink.weight + (int64_t)id * dim, lane, pieces, w);
         m_old = sink.momentum1[id];
       } else {
         slot = sink.rank[c1 - 1] - 1;
@@ -327,7 +462,8 @@ __global__ __launch_bounds__(kCombineWaves * 64) void adagrad_combine_kernel(con
     if (wave > 0) store_f32_row<VEC, NP>(shares + (int64_t)(wave - 1) * dim, lane, pieces, acc);
     __syncthreads();
     if (wave == 0) {
-      constexpr int kShareUnroll = NP >= 8 ? 1 : kCombineWaves - 1;   // eight pieces: one share at a time, or the row's registers spill
+      // eight pieces: one share at a time, or the row's registers spill; so do four next to a 16-bit table's rounding
+      constexpr int kShareUnroll = NP >= 8 || (NP >= 4 && sizeof(typename Sink::WT) == 2) ? 1 : kCombineWaves - 1;
 #pragma unroll kShareUnroll
       for (int s = 0; s < kCombineWaves - 1; ++s) {
         float v[NP][VEC];
@@ -335,7 +471,7 @@ __global__ __launch_bounds__(kCombineWaves * 64) void adagrad_combine_kernel(con
         add_row<VEC, NP>(acc, v, lane, pieces);
       }
       if constexpr (Sink::kApply)
-        apply_update<VEC, NP>(acc, w, m_old, lane, pieces, dim, sink.weight + (int64_t)id * dim, sink.momentum1 + id, sink.lr, sink.eps);
+        finish_apply<VEC, NP>(acc, w, m_old, lane, pieces, dim, id, sink);
       else
         emit_segment<VEC, NP>(acc, lane, pieces, dim, sink, id, slot);
     }
@@ -530,6 +666,30 @@ static int opt_dispatch(const OptArgs& a, const Sink& sink, const char* what) {
   return opt_launch<T, 4, (sizeof(T) == 2 ? 2 : 4)>(a, sink, what);
 }
 
+// hstu_stochastic_round: one wave per row (grid-stride), lanes own 16-byte pieces of the 16-bit row (VEC = 8; VEC = 1 for
+// rows that are no 16-byte multiples), every element rounded with the bits of (seed, row id, column)
+constexpr int kSrWaves = 4;
+template <typename W, int VEC>
+__global__ __launch_bounds__(kSrWaves * 64) void stochastic_round_kernel(const float* __restrict__ src, const int32_t* __restrict__ row_ids,
+                                                                         void* __restrict__ dst_, int64_t n, int dim, uint64_t seed) {
+  uint16_t* __restrict__ dst = (uint16_t*)dst_;
+  const int lane = threadIdx.x & 63;
+  for (int64_t i = (int64_t)blockIdx.x * kSrWaves + (threadIdx.x >> 6); i < n; i += (int64_t)gridDim.x * kSrWaves) {
+    const uint32_t row = row_ids ? (uint32_t)row_ids[i] : (uint32_t)i;
+    for (int c0 = lane * VEC; c0 < dim; c0 += 64 * VEC) {     // dim % VEC == 0: a piece is whole or absent
+      float x[VEC];
+      load_param<VEC>(x, src + i * dim + c0, true);
+      if constexpr (VEC == 1) {
+        dst[i * dim + c0] = (uint16_t)round16<W>(x[0], hstu_sr_bits(seed, row, (uint32_t)c0));
+      } else {
+        uint32_t out[VEC / 2];
+        round_piece<W, VEC>(x, seed, row, (uint32_t)(c0 / 2), out);
+        *(u32x4*)(dst + i * dim + c0) = *(const u32x4*)&out[0];
+      }
+    }
+  }
+}
+
 template <typename Sink>
 static int opt_dispatch_dtype(int dtype, const OptArgs& a, const Sink& sink, const char* what) {
   switch (dtype) {
@@ -552,13 +712,16 @@ int hstu_embedding_rowwise_adagrad_workspace_bytes(int64_t n, int32_t table_rows
   return HSTU_OK;
 }
 
-// the update behind both entry points; max_row_bytes: the widest dout row the entry point takes
+// the update behind the entry points; max_row_bytes: the widest dout row the entry point takes; weight_dtype: fp32, or a
+// 16-bit table written back by stochastic rounding with `seed`
 static int rowwise_adagrad_impl(const char* what, int max_row_bytes, const void* dout, const int32_t* idx, int64_t n, int32_t dim,
-                                int32_t table_rows, float* weight, float* momentum1, float lr, float eps, void* workspace,
-                                int64_t workspace_bytes, int dtype, void* stream) {
+                                int32_t table_rows, void* weight, int weight_dtype, float* momentum1, float lr, float eps, uint64_t seed,
+                                void* workspace, int64_t workspace_bytes, int dtype, void* stream) {
   if (!weight || !momentum1 || table_rows <= 0 || dim <= 0)
     return set_error(HSTU_EINVAL, "%s: weight and momentum1 must be non-NULL, sizes positive", what);
   if (!is_float_dtype(dtype)) return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32", what);
+  if (weight_dtype != HSTU_DTYPE_F32 && dim % 8)
+    return set_error(HSTU_EINVAL, "%s: 16-bit table rows must be 16-byte multiples (dim %d is not a multiple of 8)", what, dim);
   const int es = dtype_bytes(dtype);
   if (dim > kOptMaxDim)                             // before any product with dim: dim * es must not wrap
     return set_error(HSTU_EUNSUPPORTED, "%s: rows of %d columns > %d", what, dim, kOptMaxDim);
@@ -582,21 +745,55 @@ static int rowwise_adagrad_impl(const char* what, int max_row_bytes, const void*
   hipError_t e = sort_indices(ws + l.temp_off, temp, idx, sorted_idx, perm, n, table_rows, st);
   if (e != hipSuccess) return set_error(HSTU_ELAUNCH, "%s: sort failed: %s", what, hipGetErrorString(e));
   const OptArgs a{dout, perm, sorted_idx, n, dim, partials, st};
-  return opt_dispatch_dtype(dtype, a, ApplySink{weight, momentum1, lr, eps}, what);
+  switch (weight_dtype) {
+    case HSTU_DTYPE_F16: return opt_dispatch_dtype(dtype, a, ApplySink16<f16_t>{(f16_t*)weight, momentum1, lr, eps, seed}, what);
+    case HSTU_DTYPE_BF16: return opt_dispatch_dtype(dtype, a, ApplySink16<bf16_t>{(bf16_t*)weight, momentum1, lr, eps, seed}, what);
+    default: return opt_dispatch_dtype(dtype, a, ApplySink{(float*)weight, momentum1, lr, eps}, what);
+  }
 }
 
 int hstu_embedding_rowwise_adagrad(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows, float* weight,
                                    float* momentum1, float lr, float eps, void* workspace, int64_t workspace_bytes, int dtype,
                                    void* stream) {
-  return rowwise_adagrad_impl("hstu_embedding_rowwise_adagrad", kOptMaxPieces * 64 * 16, dout, idx, n, dim, table_rows, weight, momentum1,
-                              lr, eps, workspace, workspace_bytes, dtype, stream);
+  return rowwise_adagrad_impl("hstu_embedding_rowwise_adagrad", kOptMaxPieces * 64 * 16, dout, idx, n, dim, table_rows, weight, HSTU_DTYPE_F32,
+                              momentum1, lr, eps, 0, workspace, workspace_bytes, dtype, stream);
 }
 
 int hstu_embedding_rowwise_adagrad_coalesced(const float* G, const int32_t* rows, int64_t n, int32_t dim, int32_t table_rows,
                                              float* weight, float* momentum1, float lr, float eps, void* workspace,
                                              int64_t workspace_bytes, void* stream) {
   return rowwise_adagrad_impl("hstu_embedding_rowwise_adagrad_coalesced", kOptMaxDim * (int)sizeof(float), G, rows, n, dim, table_rows,
-                              weight, momentum1, lr, eps, workspace, workspace_bytes, HSTU_DTYPE_F32, stream);
+                              weight, HSTU_DTYPE_F32, momentum1, lr, eps, 0, workspace, workspace_bytes, HSTU_DTYPE_F32, stream);
+}
+
+int hstu_embedding_rowwise_adagrad_lowp(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows, void* weight,
+                                        int weight_dtype, float* momentum1, float lr, float eps, uint64_t seed, void* workspace,
+                                        int64_t workspace_bytes, int dtype, void* stream) {
+  const char* what = "hstu_embedding_rowwise_adagrad_lowp";
+  if (weight_dtype != HSTU_DTYPE_F16 && weight_dtype != HSTU_DTYPE_BF16)
+    return set_error(HSTU_EINVAL, "%s: weight_dtype must be fp16 or bf16 (fp32 tables: hstu_embedding_rowwise_adagrad)", what);
+  // 16-bit gradient rows of up to 4 KiB, fp32 ones (the coalesced lists) of up to 8 KiB: dim <= 2048 either way
+  const int max_row_bytes = dtype == HSTU_DTYPE_F32 ? kOptMaxDim * (int)sizeof(float) : kOptMaxPieces * 64 * 16;
+  return rowwise_adagrad_impl(what, max_row_bytes, dout, idx, n, dim, table_rows, weight, weight_dtype, momentum1, lr, eps, seed, workspace,
+                              workspace_bytes, dtype, stream);
+}
+
+int hstu_stochastic_round(const float* src, const int32_t* row_ids, void* dst, int64_t n, int32_t dim, int dst_dtype, uint64_t seed,
+                          void* stream) {
+  const char* what = "hstu_stochastic_round";
+  if (dst_dtype != HSTU_DTYPE_F16 && dst_dtype != HSTU_DTYPE_BF16) return set_error(HSTU_EINVAL, "%s: dst_dtype must be fp16 or bf16", what);
+  if (n < 0 || dim <= 0) return set_error(HSTU_EINVAL, "%s: n must be >= 0 and dim positive", what);
+  if (n == 0) return HSTU_OK;
+  if (!src || !dst) return set_error(HSTU_EINVAL, "%s: NULL input", what);
+  const bool wide = dim % 8 == 0 && !((uintptr_t)src & 15) && !((uintptr_t)dst & 15);
+  hipStream_t st = (hipStream_t)stream;
+  auto launch = [&](auto kernel) {
+    const int blocks = resident_row_blocks(kernel, kSrWaves * 64, 0, n, kSrWaves, 65535);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kSrWaves * 64), 0, st, src, row_ids, dst, n, dim, seed);
+    return check_launch(what);
+  };
+  if (dst_dtype == HSTU_DTYPE_F16) return wide ? launch(stochastic_round_kernel<f16_t, 8>) : launch(stochastic_round_kernel<f16_t, 1>);
+  return wide ? launch(stochastic_round_kernel<bf16_t, 8>) : launch(stochastic_round_kernel<bf16_t, 1>);
 }
 
 int hstu_embedding_grad_coalesce_workspace_bytes(int64_t n, int32_t table_rows, int64_t* bytes) {

@@ -77,13 +77,36 @@ class DlrmHSTUConfig:
 
 
 # ------------------------------------------------------------------------------------------- the TorchRec-shaped stand-ins
+_TABLE_DTYPES = {"FP32": torch.float32, "FP16": torch.float16, "BF16": torch.bfloat16}
+
+
+def table_dtype(data_type: Any) -> torch.dtype:
+    """The torch dtype of a table's declared ``data_type``: TorchRec's ``DataType.FP32 / FP16 / BF16`` (duck-typed: an enum
+    member's ``.name`` or ``.value``), the strings ``"FP32" / "FP16" / "BF16"`` in any case, or a torch dtype.  The
+    reference's DLRM-v3 tables are all ``DataType.FP16`` (dlrm_v3/configs.py:293-440)."""
+    if isinstance(data_type, torch.dtype):
+        if data_type in _TABLE_DTYPES.values():
+            return data_type
+    else:
+        for key in (data_type, getattr(data_type, "name", None), getattr(data_type, "value", None)):
+            if isinstance(key, str) and key.upper() in _TABLE_DTYPES:
+                return _TABLE_DTYPES[key.upper()]
+    raise ValueError(f"embedding table data_type {data_type!r} is not supported: accepted are DataType.FP32 / FP16 / BF16 (or their "
+                     f"names {sorted(_TABLE_DTYPES)}) and torch.float32 / float16 / bfloat16")
+
+
 @dataclass
 class EmbeddingConfig:
-    """the attributes of torchrec.modules.embedding_configs.EmbeddingConfig that DlrmHSTU touches"""
+    """the attributes of torchrec.modules.embedding_configs.EmbeddingConfig that DlrmHSTU touches; ``data_type``: what
+    ``table_dtype`` accepts (checked on construction)"""
     num_embeddings: int
     embedding_dim: int
     name: str = ""
     feature_names: List[str] = field(default_factory=list)
+    data_type: Any = "FP32"
+
+    def __post_init__(self) -> None:
+        table_dtype(self.data_type)
 
 
 @dataclass
@@ -154,6 +177,12 @@ class EmbeddingCollection(torch.nn.Module):
         del need_indices
         self.embeddings = torch.nn.ModuleDict(
             {t.name: torch.nn.Embedding(t.num_embeddings, t.embedding_dim, device=device) for t in tables})
+        # the declared dtype per table (no data_type attribute: fp32).  A 16-bit table is the fp32 initial values
+        # rounded to nearest: the same RNG stream gives the same table up to the cast
+        self._table_dtype: Dict[str, torch.dtype] = {t.name: table_dtype(getattr(t, "data_type", "FP32")) for t in tables}
+        for name, dtype in self._table_dtype.items():
+            if dtype != torch.float32:
+                self.embeddings[name].to(dtype)
         self._feature_to_table: Dict[str, str] = {f: t.name for t in tables for f in t.feature_names}
         self._fused: Dict[str, RowWiseAdagradConfig] = {}        # tables trained in backward (apply_rowwise_adagrad_in_backward)
 
@@ -187,44 +216,60 @@ class EmbeddingCollection(torch.nn.Module):
         for table, keys in keys_of.items():
             weight = self.embeddings[table].weight
             momentum1 = getattr(self, _momentum1_name(table))
-            if weight.dtype != torch.float32 or momentum1.dtype != torch.float32:
-                raise RuntimeError(f"table {table!r} is trained in backward and must stay float32 (got {weight.dtype}, state "
-                                   f"{momentum1.dtype}); ask for 16-bit rows with rows_dtype instead of casting the table")
+            declared = self._table_dtype.get(table, torch.float32)
+            if weight.dtype != declared or momentum1.dtype != torch.float32:
+                raise RuntimeError(f"table {table!r} is trained in backward and must stay {_dtype_name(declared)} (got {weight.dtype}, "
+                                   f"state {momentum1.dtype}); ask for 16-bit rows with rows_dtype instead of casting the table")
             ids = [features[k].values().to(torch.int64) for k in keys]
             rows = gather_rows_fused(weight, momentum1, ids[0] if len(ids) == 1 else torch.cat(ids), self._fused[table],
-                                     self._fused[table].rows_dtype)
+                                     self._fused[table].rows_dtype, getattr(self, _step_name(table), None))
             rows_of.update(zip(keys, rows.split([i.numel() for i in ids]) if len(ids) > 1 else (rows,)))
         return rows_of
 
     def apply_rowwise_adagrad_in_backward(self, lr: float, eps: float = 1e-8, weight_decay: float = 0.0,
                                           rows_dtype: Optional[torch.dtype] = None, tables: Optional[List[str]] = None,
-                                          replicated: bool = False, process_group: Any = None, average: bool = True) -> None:
+                                          replicated: bool = False, process_group: Any = None, average: bool = True,
+                                          seed: int = 0) -> None:
         apply_rowwise_adagrad_in_backward(self, lr, eps=eps, weight_decay=weight_decay, rows_dtype=rows_dtype, tables=tables,
-                                          replicated=replicated, process_group=process_group, average=average)
+                                          replicated=replicated, process_group=process_group, average=average, seed=seed)
 
     def set_learning_rate(self, lr: float) -> None:
         for cfg in self._fused.values():
             cfg.lr = float(lr)
 
     def fused_optimizer_state_dict(self) -> Dict[str, torch.Tensor]:
-        return {f"{table}.momentum1": getattr(self, _momentum1_name(table)) for table in self._fused}
+        """``"{table}.momentum1"`` per fused table, and ``"{table}.rounding_step"`` -- the int64 count of applied updates that,
+        with the configured seed, determines the next update's stochastic rounding -- per 16-bit one"""
+        state = {f"{table}.momentum1": getattr(self, _momentum1_name(table)) for table in self._fused}
+        state.update({f"{table}.rounding_step": getattr(self, _step_name(table)) for table in self._fused
+                      if hasattr(self, _step_name(table))})
+        return state
 
     def load_fused_optimizer_state_dict(self, state: Dict[str, torch.Tensor]) -> None:
-        want = {f"{table}.momentum1" for table in self._fused}
+        want = set(self.fused_optimizer_state_dict())
         if set(state) != want:
             raise KeyError(f"fused optimizer state: expected the keys {sorted(want)}, got {sorted(state)}")
         with torch.no_grad():
-            for table in self._fused:
-                getattr(self, _momentum1_name(table)).copy_(state[f"{table}.momentum1"])
+            for key, mine in self.fused_optimizer_state_dict().items():
+                mine.copy_(state[key])
 
 
 def _momentum1_name(table: str) -> str:
     return "_momentum1_" + table.replace(".", "_")
 
 
+def _step_name(table: str) -> str:
+    return "_rounding_step_" + table.replace(".", "_")
+
+
+def _dtype_name(dtype: torch.dtype) -> str:
+    return str(dtype).replace("torch.", "")
+
+
 def apply_rowwise_adagrad_in_backward(collection: Any, lr: float, eps: float = 1e-8, weight_decay: float = 0.0,
                                       rows_dtype: Optional[torch.dtype] = None, tables: Optional[List[str]] = None,
-                                      replicated: bool = False, process_group: Any = None, average: bool = True) -> None:
+                                      replicated: bool = False, process_group: Any = None, average: bool = True,
+                                      seed: int = 0) -> None:
     """Train the named tables of an ``EmbeddingCollection`` (default: all; a ``DlrmHSTU`` stands for its collection) with
     row-wise Adagrad applied in backward -- what ``apply_optimizer_in_backward(RowWiseAdagrad, ...)`` does to the reference's
     TorchRec modules (dlrm_v3/train/utils.py:190-227).  Afterwards the forward issues one gather per table, backward updates
@@ -238,7 +283,12 @@ def apply_rowwise_adagrad_in_backward(collection: Any, lr: float, eps: float = 1
     does to the dense gradients), else their sum -- in rank order on every rank, so the copies keep equal bits
     (ops/embedding.py).  PRECONDITION: the copies start identical (``ops.embedding.broadcast_fused_tables``) and every rank calls
     backward for the same tables in the same order.  Off by default: without it more than one rank is refused.  The three
-    settings are kept per table like ``lr``."""
+    settings are kept per table like ``lr``.
+
+    A table declared FP16 / BF16 (``EmbeddingConfig.data_type``) keeps its 16-bit weight and an fp32 ``momentum1``; its update
+    is computed in fp32 and written back by stochastic rounding (ops/embedding.py).  ``seed`` is the rounding's base seed; an
+    int64 count of applied updates, a second non-persistent buffer kept in host memory (reading it never waits for the
+    GPU), makes every step's draws its own.  Every table must still have the dtype it was declared with."""
     collection = getattr(collection, "_embedding_collection", collection)
     if weight_decay != 0.0:
         raise NotImplementedError(f"weight_decay = {weight_decay}: TorchRec's RowWiseAdagrad and fbgemm's exact row-wise Adagrad "
@@ -250,18 +300,23 @@ def apply_rowwise_adagrad_in_backward(collection: Any, lr: float, eps: float = 1
         if table not in collection.embeddings:
             raise KeyError(f"no embedding table named {table!r}")
         weight = collection.embeddings[table].weight
-        if weight.dtype != torch.float32:
-            raise RuntimeError(f"table {table!r} is {weight.dtype}: tables trained in backward must be float32")
+        declared = getattr(collection, "_table_dtype", {}).get(table, torch.float32)
+        if weight.dtype != declared:
+            raise RuntimeError(f"table {table!r} is {weight.dtype}: tables trained in backward must be {_dtype_name(declared)}"
+                               + ("" if declared == torch.float32 else ", the data_type they were declared with"))
     for table in names:
         if table in collection._fused:
             cfg = collection._fused[table]               # named again: this call's settings replace the table's
             cfg.lr, cfg.eps, cfg.rows_dtype = float(lr), float(eps), rows_dtype
             cfg.replicated, cfg.process_group, cfg.average = bool(replicated), process_group, bool(average)
+            cfg.seed = int(seed)
             continue
         weight = collection.embeddings[table].weight
         collection.register_buffer(_momentum1_name(table), torch.zeros(weight.shape[0], dtype=torch.float32, device=weight.device),
                                    persistent=False)
-        collection._fused[table] = RowWiseAdagradConfig(lr, eps, rows_dtype, replicated, process_group, average)
+        if weight.dtype != torch.float32:
+            collection.register_buffer(_step_name(table), torch.zeros((), dtype=torch.int64, device="cpu"), persistent=False)
+        collection._fused[table] = RowWiseAdagradConfig(lr, eps, rows_dtype, replicated, process_group, average, seed)
 
 
 def _get_supervision_labels_and_weights(

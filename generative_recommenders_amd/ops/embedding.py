@@ -15,7 +15,14 @@ without ever broadcasting them: every rank coalesces its batch to one fp32 row p
 the same update to the same concatenation in rank order.  The update is deterministic and its summation order depends
 only on that list, so equal inputs give equal bits.  PRECONDITION: the copies start identical
 (``broadcast_fused_tables``) and every rank runs backward for the same tables in the same order -- the collectives pair
-up by issue order.  ``assert_fused_tables_in_sync`` checks the outcome."""
+up by issue order.  ``assert_fused_tables_in_sync`` checks the outcome.
+
+Tables stored in 16 bits (fp16 / bf16: what the reference's configurations declare, ``data_type=DataType.FP16``) keep an
+fp32 ``momentum1``; the update is computed in fp32 -- the same fp32 value as for an fp32 table, bit for bit -- and the row is
+written back with STOCHASTIC ROUNDING (csrc/stochastic_round.h), since round-to-nearest drops every step smaller than half
+an ulp of the weight.  The random bits of an element are a function of (seed, table row, column); the seed of an update
+is ``update_seed(cfg.seed, step)`` with ``step`` the table's count of applied updates, so no two steps share their draws
+and a resumed run continues the sequence.  Replicated copies apply the same list with the same seed: equal bits again."""
 
 import ctypes as C
 from typing import Any, Dict, List, Optional, Tuple
@@ -29,37 +36,92 @@ class RowWiseAdagradConfig:
     """step size, epsilon and the dtype of the gathered rows (None: the table's) of one fused table; mutable, read at every
     forward / backward (``set_learning_rate``).  ``replicated``: every rank of ``process_group`` (None: the default group)
     holds a copy of the table and backward applies all ranks' row gradients to it, averaged over the ranks (``average``,
-    the ``GradientAllReducer`` default) or summed; off by default."""
+    the ``GradientAllReducer`` default) or summed; off by default.  ``seed``: the base seed of the stochastic rounding of a
+    16-bit table (``update_seed``); fp32 tables ignore it."""
 
     def __init__(self, lr: float, eps: float = 1e-8, rows_dtype: Optional[torch.dtype] = None, replicated: bool = False,
-                 process_group: Any = None, average: bool = True) -> None:
+                 process_group: Any = None, average: bool = True, seed: int = 0) -> None:
         self.lr = float(lr)
         self.eps = float(eps)
         self.rows_dtype = rows_dtype
         self.replicated = bool(replicated)
         self.process_group = process_group
         self.average = bool(average)
+        self.seed = int(seed)
+
+
+_M64 = (1 << 64) - 1
+
+
+def update_seed(seed: int, step: int) -> int:
+    """The 64-bit seed of a 16-bit table's update number ``step`` (0 for the first) under the base seed ``seed``: splitmix64's
+    output function on ``seed + (step + 1) * 0x9E3779B97F4A7C15`` (mod 2^64) -- a bijection of the sum, so the steps of one
+    run never share a seed: z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31."""
+    z = (int(seed) + (int(step) + 1) * 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+_LOWP = (torch.float16, torch.bfloat16)
+
+
+def stochastic_round(src: torch.Tensor, dtype: torch.dtype, seed: int, row_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``src`` (n, dim) fp32 rounded stochastically to ``dtype`` (float16 or bfloat16), element (i, c) with the random bits of
+    ``(seed, row_ids[i] if given else i, c)`` (csrc/stochastic_round.h): the cast of an fp32 table or checkpoint to a 16-bit
+    one, and the rounding a 16-bit table's update applies to its rows."""
+    L.require_gpu_tensor(src, "src")
+    if src.dtype != torch.float32 or src.dim() != 2:
+        raise RuntimeError(f"stochastic_round: src must be float32 (n, dim), got {src.dtype} {tuple(src.shape)}")
+    if dtype not in _LOWP:
+        raise RuntimeError(f"stochastic_round: dtype must be float16 or bfloat16, got {dtype}")
+    n, dim = src.shape
+    if row_ids is not None:
+        L.require_gpu_tensor(row_ids, "row_ids")
+        if row_ids.device != src.device or row_ids.shape != (n,):
+            raise RuntimeError(f"stochastic_round: row_ids ({n}) on {src.device}, got {tuple(row_ids.shape)} on {row_ids.device}")
+        row_ids = row_ids.detach().to(torch.int32).contiguous()
+    src = src.detach().contiguous()
+    dst = torch.empty((n, dim), dtype=dtype, device=src.device)
+    if n == 0 or dim == 0:
+        return dst
+    with torch.cuda.device(src.device):
+        L.check(L.lib().hstu_stochastic_round(src.data_ptr(), row_ids.data_ptr() if row_ids is not None else None, dst.data_ptr(), n,
+                                              dim, L.torch_dtype_code(dtype), int(seed) & _M64, L.current_stream_ptr(src.device)))
+    return dst
 
 
 def rowwise_adagrad_update_(weight: torch.Tensor, momentum1: torch.Tensor, idx: torch.Tensor, dout: torch.Tensor, lr: float,
-                            eps: float = 1e-8) -> None:
+                            eps: float = 1e-8, seed: Optional[int] = None) -> None:
     """in place: the update above on ``weight`` (rows, dim) fp32 and ``momentum1`` (rows) fp32 for the ids ``idx`` (n) and
     their gradient rows ``dout`` (n, dim) in bf16, fp16 or fp32.  Ids outside [0, rows) are the caller's error (not checked).
-    fp32 rows of more than 1024 columns (the coalesced lists of wide tables) go through ``hstu_embedding_rowwise_adagrad_coalesced``."""
+    fp32 rows of more than 1024 columns (the coalesced lists of wide tables) go through ``hstu_embedding_rowwise_adagrad_coalesced``.
+    A float16 / bfloat16 ``weight`` (dim a multiple of 8) is updated in fp32 and written back by stochastic rounding with the
+    random bits of ``seed``, which is then required (``update_seed``); an fp32 ``weight`` takes no seed."""
     for name, t in (("weight", weight), ("momentum1", momentum1), ("idx", idx), ("dout", dout)):
         L.require_gpu_tensor(t, name)
     if not (weight.device == momentum1.device == idx.device == dout.device):
         raise RuntimeError(f"rowwise_adagrad_update_: weight, momentum1, idx and dout must be on one device, got {weight.device}, "
                            f"{momentum1.device}, {idx.device} and {dout.device}")
-    if weight.dtype != torch.float32 or momentum1.dtype != torch.float32:
+    lowp = weight.dtype in _LOWP
+    if lowp and momentum1.dtype != torch.float32:
+        raise RuntimeError(f"rowwise_adagrad_update_: momentum1 of a {weight.dtype} table must be float32, got {momentum1.dtype}")
+    if not lowp and (weight.dtype != torch.float32 or momentum1.dtype != torch.float32):
         raise RuntimeError(f"rowwise_adagrad_update_: weight and momentum1 must be float32 (TorchRec keeps fused tables in fp32), "
                            f"got {weight.dtype} and {momentum1.dtype}")
+    if lowp and seed is None:
+        raise RuntimeError(f"rowwise_adagrad_update_: a {weight.dtype} weight is written back by stochastic rounding and needs a seed")
+    if not lowp and seed is not None:
+        raise RuntimeError("rowwise_adagrad_update_: seed is the stochastic rounding's and a float32 weight is not rounded; pass none")
     if not weight.is_contiguous() or not momentum1.is_contiguous():
         raise RuntimeError("rowwise_adagrad_update_: weight and momentum1 must be contiguous (they are updated in place)")
     if weight.dim() != 2 or momentum1.shape != (weight.shape[0],):
         raise RuntimeError(f"rowwise_adagrad_update_: weight (rows, dim) and momentum1 (rows), got {tuple(weight.shape)} and "
                            f"{tuple(momentum1.shape)}")
     rows, dim = weight.shape
+    if lowp and dim % 8:
+        raise RuntimeError(f"rowwise_adagrad_update_: rows of a {weight.dtype} weight must be 16-byte multiples (dim {dim} is not a "
+                           "multiple of 8)")
     if dout.dim() != 2 or dout.shape[1] != dim or idx.dim() != 1 or idx.shape[0] != dout.shape[0]:
         raise RuntimeError(f"rowwise_adagrad_update_: idx (n) and dout (n, {dim}), got {tuple(idx.shape)} and {tuple(dout.shape)}")
     n = idx.shape[0]
@@ -71,6 +133,12 @@ def rowwise_adagrad_update_(weight: torch.Tensor, momentum1: torch.Tensor, idx: 
     L.check(L.lib().hstu_embedding_rowwise_adagrad_workspace_bytes(n, rows, C.byref(need)))
     ws = torch.empty(max(need.value, 256), dtype=torch.uint8, device=weight.device)
     with torch.cuda.device(weight.device):
+        if lowp:
+            L.check(L.lib().hstu_embedding_rowwise_adagrad_lowp(
+                dout.data_ptr(), idx.data_ptr(), n, dim, rows, weight.data_ptr(), L.torch_dtype_code(weight.dtype), momentum1.data_ptr(),
+                float(lr), float(eps), int(seed) & _M64, ws.data_ptr(), ws.numel(), L.torch_dtype_code(dout.dtype),
+                L.current_stream_ptr(weight.device)))
+            return
         if dout.dtype == torch.float32 and dim > 1024:      # fp32 rows above 4 KiB: the coalesced lists of wide tables
             L.check(L.lib().hstu_embedding_rowwise_adagrad_coalesced(
                 dout.data_ptr(), idx.data_ptr(), n, dim, rows, weight.data_ptr(), momentum1.data_ptr(), float(lr), float(eps),
@@ -144,12 +212,21 @@ def _fused_tables(collection: Any) -> Dict[str, Tuple[torch.Tensor, torch.Tensor
     return {t: (collection.embeddings[t].weight.detach(), state[f"{t}.momentum1"].detach()) for t in collection._fused}
 
 
+def _fused_steps(collection: Any) -> Dict[str, torch.Tensor]:
+    """table name -> the int64 count of applied updates of every 16-bit fused table (``"{table}.rounding_step"``)"""
+    collection = getattr(collection, "_embedding_collection", collection)
+    state = collection.fused_optimizer_state_dict()
+    return {t: state[f"{t}.rounding_step"] for t in collection._fused if f"{t}.rounding_step" in state}
+
+
 def fused_tables_checksum(collection: Any) -> Dict[str, int]:
     """Per fused table one exact integer: the wrapping int64 sum of the fp32 bit patterns (read as int32) of ``weight`` and of
-    ``momentum1``.  Equal tables give equal sums; one flipped bit changes the sum."""
-    bits = lambda t: int(t.contiguous().view(torch.int32).sum(dtype=torch.int64))
+    ``momentum1``.  Equal tables give equal sums; one flipped bit changes the sum.  A 16-bit table's weight is summed
+    through an int16 view, and its count of applied updates is added."""
+    bits = lambda t: int(t.contiguous().view(torch.int16 if t.dtype in _LOWP else torch.int32).sum(dtype=torch.int64))
     wrap = lambda v: (v + (1 << 63)) % (1 << 64) - (1 << 63)
-    return {t: wrap(bits(w) + bits(m)) for t, (w, m) in _fused_tables(collection).items()}
+    steps = _fused_steps(collection)
+    return {t: wrap(bits(w) + bits(m) + (int(steps[t]) if t in steps else 0)) for t, (w, m) in _fused_tables(collection).items()}
 
 
 def assert_fused_tables_in_sync(collection: Any, group: Any = None) -> None:
@@ -175,14 +252,15 @@ def assert_fused_tables_in_sync(collection: Any, group: Any = None) -> None:
 
 
 def broadcast_fused_tables(collection: Any, src: int = 0, group: Any = None) -> None:
-    """Step 0 of replicated training: every rank's fused tables and their ``momentum1`` become rank ``src``'s (a collective;
-    staged through host memory on backends other than ``nccl``)."""
+    """Step 0 of replicated training: every rank's fused tables and their ``momentum1`` become rank ``src``'s, and so does a
+    16-bit table's count of applied updates (a collective; staged through host memory on backends other than ``nccl``)."""
     dist = torch.distributed
     on_device = dist.get_backend(group) == "nccl"
+    steps = _fused_steps(collection)
     with torch.no_grad():
-        for weight, momentum1 in _fused_tables(collection).values():
-            for t in (weight, momentum1):
-                buf = t if on_device else t.cpu()
+        for table, (weight, momentum1) in _fused_tables(collection).items():
+            for t in (weight, momentum1) + ((steps[table],) if table in steps else ()):
+                buf = t.to(weight.device) if on_device else t.cpu()
                 dist.broadcast(buf, src=src, group=group)
                 if buf is not t:
                     t.copy_(buf)
@@ -198,9 +276,10 @@ def _refuse_replicated_tables() -> None:
 
 class _GatherRowsFusedFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, weight, momentum1, idx, cfg, rows_dtype):
+    def forward(ctx, weight, momentum1, idx, cfg, rows_dtype, step=None):
         ctx.save_for_backward(idx)
         ctx.table = (weight, momentum1, cfg)        # the parameter and its state themselves: the update is in place
+        ctx.step = step                             # a 16-bit table's count of applied updates (int64, in place too)
         rows = weight.index_select(0, idx)
         return rows if rows_dtype is None else rows.to(rows_dtype)
 
@@ -208,6 +287,15 @@ class _GatherRowsFusedFunction(torch.autograd.Function):
     def backward(ctx, g):
         (idx,) = ctx.saved_tensors
         weight, momentum1, cfg = ctx.table
+        step, seed = ctx.step, None
+        none = (None,) * (5 if step is None else 6)
+        if weight.dtype in _LOWP:
+            if step is None:
+                raise RuntimeError(f"a {weight.dtype} table trained in backward needs its step counter (gather_rows_fused's step)")
+            if idx.numel() == 0 and not getattr(cfg, "replicated", False):
+                return none                         # an empty batch applies nothing and does not count
+            seed = update_seed(getattr(cfg, "seed", 0), int(step))
+        rounding = {} if seed is None else {"seed": seed}       # fp32 tables: the call is the one it was
         dist = torch.distributed
         if getattr(cfg, "replicated", False) and dist.is_available() and dist.is_initialized():
             # every rank applies every rank's row gradients, in rank order: the copies of the table keep equal bits.  The
@@ -217,16 +305,24 @@ class _GatherRowsFusedFunction(torch.autograd.Function):
             with torch.no_grad():
                 rows, G, count = coalesce_row_gradients(idx, g, weight.shape[0], scale)
                 rows_all, G_all = exchange_row_gradients(rows, G, count, group)
-                rowwise_adagrad_update_(weight, momentum1, rows_all, G_all, cfg.lr, cfg.eps)
-            return None, None, None, None, None
+                rowwise_adagrad_update_(weight, momentum1, rows_all, G_all, cfg.lr, cfg.eps, **rounding)
+                if seed is not None and rows_all.numel() > 0:      # the same list on every rank: the same count
+                    step += 1
+            return none
         _refuse_replicated_tables()
         with torch.no_grad():
-            rowwise_adagrad_update_(weight, momentum1, idx, g, cfg.lr, cfg.eps)
-        return None, None, None, None, None
+            rowwise_adagrad_update_(weight, momentum1, idx, g, cfg.lr, cfg.eps, **rounding)
+            if seed is not None:
+                step += 1
+        return none
 
 
 def gather_rows_fused(weight: torch.Tensor, momentum1: torch.Tensor, idx: torch.Tensor, cfg: Any,
-                      rows_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+                      rows_dtype: Optional[torch.dtype] = None, step: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``weight[idx]`` (cast to ``rows_dtype`` when given) whose backward applies the row-wise Adagrad step of ``cfg`` (``lr``,
-    ``eps``) to ``weight`` and ``momentum1`` in place and hands autograd no gradient for the table: ``weight.grad`` stays None."""
-    return _GatherRowsFusedFunction.apply(weight, momentum1, idx, cfg, rows_dtype)
+    ``eps``) to ``weight`` and ``momentum1`` in place and hands autograd no gradient for the table: ``weight.grad`` stays None.
+    A float16 / bfloat16 ``weight`` needs ``step``, its int64 count of applied updates: backward rounds with
+    ``update_seed(cfg.seed, step)`` and adds 1 to it (an empty batch applies nothing and does not count)."""
+    if step is None:
+        return _GatherRowsFusedFunction.apply(weight, momentum1, idx, cfg, rows_dtype)
+    return _GatherRowsFusedFunction.apply(weight, momentum1, idx, cfg, rows_dtype, step)

@@ -430,6 +430,24 @@ int hstu_embedding_rowwise_adagrad(const void* dout, const int32_t* idx, int64_t
 int hstu_embedding_rowwise_adagrad_coalesced(const float* G, const int32_t* rows, int64_t n, int32_t dim, int32_t table_rows,
                                              float* weight, float* momentum1, float lr, float eps, void* workspace,
                                              int64_t workspace_bytes, void* stream);
+/* The same update on a table stored in 16 bits (what the reference's DLRM-v3 configurations declare: data_type = FP16):
+ * weight (table_rows, dim) in `weight_dtype` (HSTU_DTYPE_F16 or HSTU_DTYPE_BF16), momentum1 (table_rows) fp32.  A touched row is
+ * widened to fp32, updated by exactly the arithmetic above -- for a table holding the same values in fp32,
+ * hstu_embedding_rowwise_adagrad[_coalesced] computes the same fp32 row and the same momentum1 bit for bit -- and written
+ * back by STOCHASTIC ROUNDING (csrc/stochastic_round.h states the rule): element (r, c) is rounded with the 16 random bits
+ * hstu_sr_bits(seed, r, c), a function of the seed, the TABLE row and the column alone, so the result does not depend on
+ * the batch order beyond what the sum does, and is bit-identical from run to run.  The caller passes a fresh seed per
+ * step.  dim a multiple of 8 and <= 2048; dout (n, dim) in `dtype`: bf16 / fp16 rows, or fp32 rows of up to 8 KiB (both
+ * domains of the fp32-table pair above).  Workspace: hstu_embedding_rowwise_adagrad_workspace_bytes. */
+int hstu_embedding_rowwise_adagrad_lowp(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows,
+                                        void* weight, int weight_dtype, float* momentum1, float lr, float eps, uint64_t seed,
+                                        void* workspace, int64_t workspace_bytes, int dtype, void* stream);
+/* dst[i, c] = the stochastic rounding of src[i, c] to `dst_dtype` (HSTU_DTYPE_F16 or HSTU_DTYPE_BF16) with the random bits
+ * hstu_sr_bits(seed, row_ids ? row_ids[i] : i, c): the cast of an fp32 table or checkpoint to a 16-bit one, and the rule of
+ * the update above on its own.  src (n, dim) fp32, dst (n, dim), any dim >= 1 (16-byte pieces when dim is a multiple of 8
+ * and both are 16-byte aligned); row_ids (n) int32 or NULL; n == 0 touches nothing. */
+int hstu_stochastic_round(const float* src, const int32_t* row_ids, void* dst, int64_t n, int32_t dim, int dst_dtype,
+                          uint64_t seed, void* stream);
 /* The first half of that update alone, for data-parallel ranks that exchange their row gradients before applying them:
  * the batch's (idx, dout) coalesced to one fp32 row per distinct id.
  *   rows[s]  = the s-th smallest distinct id of idx (ascending), s < u = *count

@@ -20,8 +20,13 @@ does per step -- coalesce ITS shard, then the merged update -- is timed against 
 one shard, all in one process, alternating.  ``sent_bytes`` is what a rank puts on the wire, u * (4 + 4 * dim) for its u
 distinct ids, beside the raw alternative n / W * (4 + es * dim); the exchange itself is not timed (one GPU).
 
+--table-dtype fp16 | bf16 times the update of a table stored in 16 bits (the fp32 update of the widened row, written back by
+stochastic rounding) against the fp32 table's, the two alternating in one process on the same ids and gradient rows.  The
+16-bit table's algorithmic bytes: n * dim * sizeof(dout) + unique * (2 * dim * 2 + 8).
+
     python tools/bench_embedding_optimizer.py [--iters 10] [--rounds 7] [--out profiles/r15_bench_embedding_optimizer.json]
     python tools/bench_embedding_optimizer.py --replicated 8 --out profiles/r17_bench_embedding_replicated.json
+    python tools/bench_embedding_optimizer.py --table-dtype fp16 --out profiles/r18_bench_embedding_lowp_fp16.json
 """
 import argparse
 import json
@@ -107,6 +112,42 @@ def run(rows, n, dense, iters, rounds):
     return res
 
 
+def run_lowp(rows, n, table_dtype, iters, rounds):
+    g = torch.Generator(device=DEV).manual_seed(0)
+    idx = _zipf_ids(rows, n, g)
+    idx32 = idx.to(torch.int32)
+    unique = int((torch.bincount(idx, minlength=1) > 0).sum())
+    dout = (0.01 * torch.randn(n, DIM, device=DEV, generator=g)).to(torch.bfloat16)
+    w32 = torch.randn(rows, DIM, device=DEV, generator=g)
+    w16 = w32.to(table_dtype)
+    m32, m16 = torch.zeros(rows, device=DEV), torch.zeros(rows, device=DEV)
+    step = [0]
+
+    def lowp():
+        step[0] += 1                                               # a fresh seed per call, as in training
+        rowwise_adagrad_update_(w16, m16, idx32, dout, LR, EPS, seed=step[0])
+
+    name16 = str(table_dtype).replace("torch.", "")
+    paths = {"float32": lambda: rowwise_adagrad_update_(w32, m32, idx32, dout, LR, EPS), name16: lowp}
+    for fn in paths.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in paths}
+    for _ in range(rounds):
+        for name, fn in paths.items():
+            times[name].append(_events_ms(fn, iters))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    alg = {"float32": n * DIM * dout.element_size() + unique * (2 * DIM * 4 + 8), name16: n * DIM * dout.element_size() + unique * (2 * DIM * 2 + 8)}
+    return {"shape": {"table_rows": rows, "dim": DIM, "n": n, "unique_ids": unique, "dout": "bfloat16", "table": name16},
+            "algorithmic_bytes": alg,
+            "us": {k: round(1e3 * v, 2) for k, v in med.items()},
+            "us_rounds": {k: [round(1e3 * x, 2) for x in v] for k, v in times.items()},
+            "GBps": {k: round(alg[k] / (1e-3 * med[k]) / 1e9, 1) for k in med},
+            "lowp_over_float32": round(med[name16] / med["float32"], 3),
+            "lowp_over_float32_rounds": [round(a / b, 3) for a, b in zip(times[name16], times["float32"])]}
+
+
 def run_replicated(rows, n, world, iters, rounds):
     g = torch.Generator(device=DEV).manual_seed(0)
     idx32 = _zipf_ids(rows, n, g).to(torch.int32)
@@ -152,12 +193,17 @@ def main():
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--out", default=None)
     ap.add_argument("--replicated", type=int, default=0, metavar="W", help="time the replicated-table path with W emulated ranks")
+    ap.add_argument("--table-dtype", choices=["fp32", "fp16", "bf16"], default="fp32",
+                    help="fp16 / bf16: time the 16-bit table's update against the fp32 table's, alternating in one process")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_embedding_optimizer: needs a GPU (a timing without one says nothing)")
     res = {"device": torch.cuda.get_device_name(0), "iters": args.iters, "rounds": args.rounds, "workloads": {}}
     for name in args.shapes.split(","):
-        if args.replicated > 0:
+        if args.table_dtype != "fp32":
+            res["workloads"][name] = run_lowp(*SHAPES[name][:2], {"fp16": torch.float16, "bf16": torch.bfloat16}[args.table_dtype],
+                                              args.iters, args.rounds)
+        elif args.replicated > 0:
             res["workloads"][name] = run_replicated(*SHAPES[name][:2], args.replicated, args.iters, args.rounds)
         else:
             res["workloads"][name] = run(*SHAPES[name], args.iters, args.rounds)
