@@ -139,6 +139,9 @@ SIGNATURES = {
     "hstu_embedding_rowwise_adagrad_coalesced": (_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _f32, _f32, _vp, _i64, _vp]),
     "hstu_embedding_rowwise_adagrad_lowp": (_int, [_vp, _vp, _i64, _i32, _i32, _vp, _int, _vp, _f32, _f32, C.c_uint64, _vp, _i64, _int,
                                                   _vp]),
+    "hstu_embedding_sparse_sgd": (_int, [_vp, _vp, _i64, _i32, _i32, _vp, _int, _f32, C.c_uint64, _vp, _i64, _int, _vp]),
+    "hstu_embedding_sparse_adam": (_int, [_vp, _vp, _i64, _i32, _i32, _vp, _int, _vp, _vp, _f32, _f32, _f32, _f32, _i64, C.c_uint64,
+                                         _vp, _i64, _int, _vp]),
     "hstu_stochastic_round": (_int, [_vp, _vp, _vp, _i64, _i32, _int, C.c_uint64, _vp]),
     "hstu_embedding_grad_coalesce_workspace_bytes": (_int, [_i64, _i32, _vp]),
     "hstu_embedding_grad_coalesce": (_int, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _i64, _int, _vp]),

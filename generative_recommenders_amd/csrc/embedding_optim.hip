@@ -34,6 +34,16 @@
 // there the row is widened to fp32, updated by apply_update's arithmetic -- the fp32 result equals the fp32 table's bit for
 // bit -- and written back through the stochastic rounding of stochastic_round.h, whose random bits are a function of
 // (seed, table row, column) alone.  momentum1 stays fp32.
+//
+// Sparse SGD and sparse Adam (hstu_embedding_sparse_sgd / hstu_embedding_sparse_adam; the other two choices of the reference's
+// sparse_optimizer_factory_and_class) are two more endings of the same walk: SgdSink<W> and AdamSink<W>, W the table's element
+// type.  What travels with a group of gradient rows is the sink's business (its Pre record, prefetch / finish): Adagrad
+// the table row and its scalar, SGD the table row, the coalesce its slot.  Adam prefetches the table row ONLY and reads
+// exp_avg / exp_avg_sq of the row where the segment ends: prefetched like the table row they would be 128 more registers at
+// the reference's row width (dim 256, 16-bit gradients, eight rows in flight: 8 + 32 + 64 are held already), which leaves
+// the wave alone on its SIMD, while the loads at the segment's end are hidden by the other waves the smaller kernel leaves
+// room for.  The arithmetic of one element (adam_element, sgd_element) is the same function for every table type and for
+// both kernels, its multiply-adds pinned by fmaf, so a 16-bit table's fp32 row, exp_avg and exp_avg_sq equal the fp32 table's.
 #include "hstu_common.cuh"
 #include "capi_internal.h"
 #include "embedding_sort.cuh"
@@ -148,45 +158,6 @@ __device__ __forceinline__ void apply_update(const float (&acc)[NP][VEC], float 
   if (lane == 0) *m_ptr = m_new;
 }
 
-// What the chunk and combine kernels do with a finished segment: apply it to the table (the update) ...
-struct ApplySink {
-  static constexpr bool kApply = true;
-  typedef float WT;
-  float *weight, *momentum1;
-  float lr, eps;
-};
-// ... to a table of 16-bit rows (W: f16_t or bf16_t), written back by stochastic rounding ...
-template <typename W>
-struct ApplySink16 {
-  static constexpr bool kApply = true;
-  typedef W WT;
-  W* weight;
-  float* momentum1;
-  float lr, eps;
-  uint64_t seed;
-};
-// ... or write it out (the coalesce): rank[p] = number of segment heads among the sorted positions 0 .. p, the same for
-// every position of a segment, so any of them names the segment's slot rank[p] - 1
-struct EmitSink {
-  static constexpr bool kApply = false;
-  typedef float WT;
-  int32_t* rows;
-  float* G;
-  const int32_t* rank;
-  float scale;
-};
-
-template <int VEC, int NP>
-__device__ __forceinline__ void emit_segment(const float (&acc)[NP][VEC], int lane, int pieces, int dim, const EmitSink& s, int id, int slot) {
-  float out[NP][VEC];
-#pragma unroll
-  for (int j = 0; j < NP; ++j)
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) out[j][c] = s.scale * acc[j][c];
-  store_f32_row<VEC, NP>(s.G + (int64_t)slot * dim, lane, pieces, out);
-  if (lane == 0) s.rows[slot] = id;
-}
-
 // The registers a prefetched table row waits in: fp32 as loaded, or the raw 16-bit elements, two per register (VEC / 2
 // registers per piece: 16 bytes per lane and piece next to 16-bit gradient rows, 8 bytes next to fp32 ones)
 template <typename WT, int VEC, int NP>
@@ -266,43 +237,245 @@ __device__ __forceinline__ void round_piece(const float (&x)[VEC], uint64_t seed
   }
 }
 
-// the finished segment of table row `id` applied to the table: the fp32 table's update as it is ...
-template <int VEC, int NP>
-__device__ __forceinline__ void finish_apply(const float (&acc)[NP][VEC], float (&w)[NP][VEC], float m_old, int lane, int pieces, int dim,
-                                             int id, const ApplySink& s) {
-  apply_update<VEC, NP>(acc, w, m_old, lane, pieces, dim, s.weight + (int64_t)id * dim, s.momentum1 + id, s.lr, s.eps);
-}
-// ... and the 16-bit table's: apply_update's arithmetic on the widened row (the multiply-add contracted as the compiler
-// contracts it there, pinned by fmaf), every element then rounded with its own 16 random bits -- one hash per column pair
-// (round_piece)
-template <int VEC, int NP, typename W>
-__device__ __forceinline__ void finish_apply(const float (&acc)[NP][VEC], const uint32_t (&raw)[NP][VEC / 2], float m_old, int lane, int pieces,
-                                             int dim, int id, const ApplySink16<W>& s) {
-  const float ss = row_sum_of_squares<VEC, NP>(acc, lane, pieces);
-  const float m_new = m_old + ss / (float)dim;
-  const float step = s.lr / (sqrtf(m_new) + s.eps);
-  W* __restrict__ w_row = s.weight + (int64_t)id * dim;
+// piece j of a prefetched table row as fp32 (a 16-bit table's is widened) ...
+template <typename WT, int VEC, int NP>
+__device__ __forceinline__ void widen_piece(const typename WRow<WT, VEC, NP>::type& w, int j, float (&x)[VEC]) {
+  if constexpr (sizeof(WT) == 2) {
 #pragma unroll
-  for (int j = 0; j < NP; ++j) {
-    const int p = lane + 64 * j;
-    if (p < pieces) {
-      float x[VEC];
-      uint32_t out[VEC / 2];
-#pragma unroll
-      for (int c = 0; c < VEC / 2; ++c) {
-        x[2 * c] = fmaf(-step, acc[j][2 * c], widen16<W>(raw[j][c] & 0xffffu));
-        x[2 * c + 1] = fmaf(-step, acc[j][2 * c + 1], widen16<W>(raw[j][c] >> 16));
-      }
-      round_piece<W, VEC>(x, s.seed, (uint32_t)id, (uint32_t)(p * (VEC / 2)), out);
-      if constexpr (VEC == 8) *(u32x4*)(w_row + (int64_t)p * VEC) = *(const u32x4*)&out[0];
-      else *(u32x2*)(w_row + (int64_t)p * VEC) = *(const u32x2*)&out[0];
+    for (int c = 0; c < VEC / 2; ++c) {
+      x[2 * c] = widen16<WT>(w[j][c] & 0xffffu);
+      x[2 * c + 1] = widen16<WT>(w[j][c] >> 16);
     }
+  } else {
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) x[c] = w[j][c];
   }
-  if (lane == 0) s.momentum1[id] = m_new;
+}
+// ... and piece p of table row `id` written back: as it is, or every element rounded with its own 16 random bits -- one hash per
+// column pair (round_piece)
+template <typename WT, int VEC>
+__device__ __forceinline__ void write_piece(WT* __restrict__ w_row, int p, const float (&x)[VEC], uint64_t seed, int id) {
+  if constexpr (sizeof(WT) == 2) {
+    uint32_t out[VEC / 2];
+    round_piece<WT, VEC>(x, seed, (uint32_t)id, (uint32_t)(p * (VEC / 2)), out);
+    if constexpr (VEC == 8) *(u32x4*)(w_row + (int64_t)p * VEC) = *(const u32x4*)&out[0];
+    else *(u32x2*)(w_row + (int64_t)p * VEC) = *(const u32x2*)&out[0];
+  } else {
+#pragma unroll
+    for (int c = 0; c < VEC; c += 4) *(float4*)(w_row + (int64_t)p * VEC + c) = *(const float4*)&x[c];
+  }
 }
 
+// What the chunk and combine kernels do with a finished segment is their Sink.  A sink names what travels with a group of
+// gradient rows for every segment that ends in the group (Pre, filled by prefetch: table row `id`, whose segment ends at the
+// sorted position `pos`) and what happens at the segment's end (finish: acc = G[id, :]).
+//
+// Row-wise Adagrad on an fp32 table: the table row and momentum1[id] travel ...
+struct ApplySink {
+  static constexpr bool kApply = true;
+  typedef float WT;
+  float *weight, *momentum1;
+  float lr, eps;
+  template <int VEC, int NP>
+  struct Pre {
+    float w[NP][VEC];
+    float m_old = 0.f;
+  };
+  template <int VEC, int NP>
+  __device__ __forceinline__ void prefetch(Pre<VEC, NP>& pre, int id, int64_t pos, int lane, int pieces, int dim) const {
+    load_w_row<VEC, NP>(weight + (int64_t)id * dim, lane, pieces, pre.w);
+    pre.m_old = momentum1[id];
+  }
+  template <int VEC, int NP>
+  __device__ __forceinline__ void finish(const float (&acc)[NP][VEC], Pre<VEC, NP>& pre, int id, int lane, int pieces, int dim) const {
+    apply_update<VEC, NP>(acc, pre.w, pre.m_old, lane, pieces, dim, weight + (int64_t)id * dim, momentum1 + id, lr, eps);
+  }
+};
+// ... on a table of 16-bit rows (W: f16_t or bf16_t): apply_update's arithmetic on the widened row (the multiply-add
+// contracted as the compiler contracts it there, pinned by fmaf), written back by stochastic rounding ...
+template <typename W>
+struct ApplySink16 {
+  static constexpr bool kApply = true;
+  typedef W WT;
+  W* weight;
+  float* momentum1;
+  float lr, eps;
+  uint64_t seed;
+  template <int VEC, int NP>
+  struct Pre {
+    uint32_t w[NP][VEC / 2];
+    float m_old = 0.f;
+  };
+  template <int VEC, int NP>
+  __device__ __forceinline__ void prefetch(Pre<VEC, NP>& pre, int id, int64_t pos, int lane, int pieces, int dim) const {
+    load_w_row<VEC, NP>(weight + (int64_t)id * dim, lane, pieces, pre.w);
+    pre.m_old = momentum1[id];
+  }
+  template <int VEC, int NP>
+  __device__ __forceinline__ void finish(const float (&acc)[NP][VEC], Pre<VEC, NP>& pre, int id, int lane, int pieces, int dim) const {
+    const float ss = row_sum_of_squares<VEC, NP>(acc, lane, pieces);
+    const float m_new = pre.m_old + ss / (float)dim;
+    const float step = lr / (sqrtf(m_new) + eps);
+    W* __restrict__ w_row = weight + (int64_t)id * dim;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      const int p = lane + 64 * j;
+      if (p < pieces) {
+        float x[VEC];
+#pragma unroll
+        for (int c = 0; c < VEC / 2; ++c) {
+          x[2 * c] = fmaf(-step, acc[j][2 * c], widen16<W>(pre.w[j][c] & 0xffffu));
+          x[2 * c + 1] = fmaf(-step, acc[j][2 * c + 1], widen16<W>(pre.w[j][c] >> 16));
+        }
+        write_piece<W, VEC>(w_row, p, x, seed, id);
+      }
+    }
+    if (lane == 0) momentum1[id] = m_new;
+  }
+};
+
+// ... SGD, W[r, :] -= lr * G[r, :], on a table of fp32 or 16-bit rows (WT: float, f16_t or bf16_t): the table row travels ...
+__device__ __forceinline__ float sgd_element(float g, float w, float lr) { return fmaf(-lr, g, w); }
+
+template <typename W>
+struct SgdSink {
+  static constexpr bool kApply = true;
+  typedef W WT;
+  W* weight;
+  float lr;
+  uint64_t seed;
+  template <int VEC, int NP>
+  struct Pre {
+    typename WRow<W, VEC, NP>::type w;
+  };
+  template <int VEC, int NP>
+  __device__ __forceinline__ void prefetch(Pre<VEC, NP>& pre, int id, int64_t pos, int lane, int pieces, int dim) const {
+    load_w_row<VEC, NP>(weight + (int64_t)id * dim, lane, pieces, pre.w);
+  }
+  template <int VEC, int NP>
+  __device__ __forceinline__ void finish(const float (&acc)[NP][VEC], Pre<VEC, NP>& pre, int id, int lane, int pieces, int dim) const {
+    W* __restrict__ w_row = weight + (int64_t)id * dim;
+    if constexpr (sizeof(W) == 4) {                 // in the prefetched row's own registers, stored as apply_update stores it
+#pragma unroll
+      for (int j = 0; j < NP; ++j)
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) pre.w[j][c] = sgd_element(acc[j][c], pre.w[j][c], lr);
+      store_f32_row<VEC, NP>(w_row, lane, pieces, pre.w);
+    } else {
+#pragma unroll
+      for (int j = 0; j < NP; ++j) {
+        const int p = lane + 64 * j;
+        if (p < pieces) {
+          float x[VEC];
+          widen_piece<W, VEC, NP>(pre.w, j, x);
+#pragma unroll
+          for (int c = 0; c < VEC; ++c) x[c] = sgd_element(acc[j][c], x[c], lr);
+          write_piece<W, VEC>(w_row, p, x, seed, id);
+        }
+      }
+    }
+  }
+};
+
+// ... Adam (torch.optim.Adam's arithmetic, amsgrad off, applied to the touched rows only).  The host forms the bias corrections
+// 1 - beta^t in double and hands over: one_minus_beta = (float)(1 - beta), step_size = lr / (float)bc1, sqrt_bc2 =
+// sqrtf((float)bc2).  One element, the same function for every table type and both kernels; IEEE sqrt and divide, every
+// multiply-add pinned:
+struct AdamCoef {
+  float beta1, one_minus_beta1, beta2, one_minus_beta2, step_size, sqrt_bc2, eps;
+};
+__device__ __forceinline__ float adam_element(float g, float& m, float& v, float w, const AdamCoef& k) {
+#pragma clang fp contract(off)
+  m = fmaf(k.beta1, m, k.one_minus_beta1 * g);
+  v = fmaf(k.beta2, v, (k.one_minus_beta2 * g) * g);
+  return w - (k.step_size * m) / (sqrtf(v) / k.sqrt_bc2 + k.eps);
+}
+
+// The table row travels with the gradient rows; exp_avg[id, :] and exp_avg_sq[id, :] are read where the segment ends, piece by
+// piece (see the head of this file for why)
+template <typename W>
+struct AdamSink {
+  static constexpr bool kApply = true;
+  typedef W WT;
+  W* weight;
+  float *exp_avg, *exp_avg_sq;
+  AdamCoef k;
+  uint64_t seed;
+  template <int VEC, int NP>
+  struct Pre {
+    typename WRow<W, VEC, NP>::type w;
+  };
+  template <int VEC, int NP>
+  __device__ __forceinline__ void prefetch(Pre<VEC, NP>& pre, int id, int64_t pos, int lane, int pieces, int dim) const {
+    load_w_row<VEC, NP>(weight + (int64_t)id * dim, lane, pieces, pre.w);
+  }
+  template <int VEC, int NP>
+  __device__ __forceinline__ void finish(const float (&acc)[NP][VEC], Pre<VEC, NP>& pre, int id, int lane, int pieces, int dim) const {
+    W* __restrict__ w_row = weight + (int64_t)id * dim;
+    float* __restrict__ m_row = exp_avg + (int64_t)id * dim;
+    float* __restrict__ v_row = exp_avg_sq + (int64_t)id * dim;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      const int p = lane + 64 * j;
+      if (p < pieces) {
+        float x[VEC], m[VEC], v[VEC];
+#pragma unroll
+        for (int c = 0; c < VEC; c += 4) {
+          *(float4*)&m[c] = *(const float4*)(m_row + (int64_t)p * VEC + c);
+          *(float4*)&v[c] = *(const float4*)(v_row + (int64_t)p * VEC + c);
+        }
+        widen_piece<W, VEC, NP>(pre.w, j, x);
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) x[c] = adam_element(acc[j][c], m[c], v[c], x[c], k);
+#pragma unroll
+        for (int c = 0; c < VEC; c += 4) {
+          *(float4*)(m_row + (int64_t)p * VEC + c) = *(const float4*)&m[c];
+          *(float4*)(v_row + (int64_t)p * VEC + c) = *(const float4*)&v[c];
+        }
+        if constexpr (sizeof(W) == 4) {             // back into the prefetched row's own registers, stored below as apply_update stores it
+#pragma unroll
+          for (int c = 0; c < VEC; ++c) pre.w[j][c] = x[c];
+        } else {
+          write_piece<W, VEC>(w_row, p, x, seed, id);
+        }
+      }
+    }
+    if constexpr (sizeof(W) == 4) store_f32_row<VEC, NP>(w_row, lane, pieces, pre.w);
+  }
+};
+
+// ... or write it out (the coalesce): scale * G[r, :] and r at the segment's rank among the segment heads.  rank[p] = number of
+// segment heads among the sorted positions 0 .. p, the same for every position of a segment, so any of them names the
+// segment's slot rank[p] - 1, which travels
+struct EmitSink {
+  static constexpr bool kApply = false;
+  typedef float WT;
+  int32_t* rows;
+  float* G;
+  const int32_t* rank;
+  float scale;
+  template <int VEC, int NP>
+  struct Pre {
+    int slot = 0;
+  };
+  template <int VEC, int NP>
+  __device__ __forceinline__ void prefetch(Pre<VEC, NP>& pre, int id, int64_t pos, int lane, int pieces, int dim) const {
+    pre.slot = rank[pos] - 1;
+  }
+  template <int VEC, int NP>
+  __device__ __forceinline__ void finish(const float (&acc)[NP][VEC], Pre<VEC, NP>& pre, int id, int lane, int pieces, int dim) const {
+    float out[NP][VEC];
+#pragma unroll
+    for (int j = 0; j < NP; ++j)
+#pragma unroll
+      for (int c = 0; c < VEC; ++c) out[j][c] = scale * acc[j][c];
+    store_f32_row<VEC, NP>(G + (int64_t)pre.slot * dim, lane, pieces, out);
+    if (lane == 0) rows[pre.slot] = id;
+  }
+};
+
 template <typename T, int NP, int U, int kChunk, typename Sink>
-__global__ __launch_bounds__(kOptWaves * 64) void adagrad_chunk_kernel(const T* __restrict__ g, const int32_t* __restrict__ perm,
+__global__ __launch_bounds__(kOptWaves * 64) void optim_chunk_kernel(const T* __restrict__ g, const int32_t* __restrict__ perm,
                                                                        const int32_t* __restrict__ sorted_idx, int64_t n, int dim,
                                                                        float* __restrict__ partials, Sink sink) {
   constexpr int VEC = 16 / (int)sizeof(T);
@@ -335,9 +508,8 @@ __global__ __launch_bounds__(kOptWaves * 64) void adagrad_chunk_kernel(const T* 
       for (int c = 0; c < VEC; ++c) acc[j][c] = 0.f;
     for (int r0 = 0; r0 < cnt; r0 += U) {
       u32x4 v[U][NP];
-      typename WRow<typename Sink::WT, VEC, NP>::type w[U];
-      float m_old[U];
-      int id[U], slot[U];
+      typename Sink::template Pre<VEC, NP> pre[U];
+      int id[U];
       bool ends[U], whole[U];
       bool began_before = open_left;                // of the segment that row u belongs to
 #pragma unroll
@@ -355,16 +527,7 @@ __global__ __launch_bounds__(kOptWaves * 64) void adagrad_chunk_kernel(const T* 
           const int p = lane + 64 * j;
           if (p < pieces) v[u][j] = *(const u32x4*)(row + 16 * p);
         }
-        m_old[u] = 0.f;
-        slot[u] = 0;
-        if constexpr (Sink::kApply) {
-          if (whole[u]) {                           // the table row travels with the gradient rows
-            load_w_row<VEC, NP>(sink.weight + (int64_t)id[u] * dim, lane, pieces, w[u]);
-            m_old[u] = sink.momentum1[id[u]];
-          }
-        } else {
-          if (whole[u]) slot[u] = sink.rank[c0 + q] - 1;   // so does the segment's slot
-        }
+        if (whole[u]) sink.template prefetch<VEC, NP>(pre[u], id[u], c0 + q, lane, pieces, dim);   // travels with the gradient rows
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -379,10 +542,7 @@ __global__ __launch_bounds__(kOptWaves * 64) void adagrad_chunk_kernel(const T* 
         }
         if (ends[u]) {
           if (whole[u]) {
-            if constexpr (Sink::kApply)
-              finish_apply<VEC, NP>(acc, w[u], m_old[u], lane, pieces, dim, id[u], sink);
-            else
-              emit_segment<VEC, NP>(acc, lane, pieces, dim, sink, id[u], slot[u]);
+            sink.template finish<VEC, NP>(acc, pre[u], id[u], lane, pieces, dim);
           } else {
             store_f32_row<VEC, NP>(partials + (2 * b + (open_left ? 0 : 1)) * dim, lane, pieces, acc);
           }
@@ -402,7 +562,7 @@ __global__ __launch_bounds__(kOptWaves * 64) void adagrad_chunk_kernel(const T* 
 // k up to the first one the segment does not leave.  Wave w adds the w-th share of that list; wave 0 adds the shares in wave
 // order.  (Every condition below is the same in all threads of the workgroup: the barriers are reached by all or none.)
 template <int VEC, int NP, int kChunk, typename Sink>
-__global__ __launch_bounds__(kCombineWaves * 64) void adagrad_combine_kernel(const int32_t* __restrict__ sorted_idx, int64_t n, int dim,
+__global__ __launch_bounds__(kCombineWaves * 64) void optim_combine_kernel(const int32_t* __restrict__ sorted_idx, int64_t n, int dim,
                                                                              const float* __restrict__ partials, Sink sink) {
   extern __shared__ __attribute__((aligned(16))) float shares[];       // (kCombineWaves - 1) rows of dim floats
   constexpr int U = NP >= 8 ? 1 : NP * VEC >= 32 ? 2 : NP * VEC >= 16 ? 4 : 8;   // partial sums in flight: 64 registers (32 in eight pieces)
@@ -430,18 +590,9 @@ __global__ __launch_bounds__(kCombineWaves * 64) void adagrad_combine_kernel(con
     const int64_t total = last - b + 1;                      // list item 0: slot (b, 1); item i > 0: slot (b + i, 0)
     const int64_t share = (total + kCombineWaves - 1) / kCombineWaves;
     const int64_t i0 = wave * share, i1 = min(total, i0 + share);
-    typename WRow<typename Sink::WT, VEC, NP>::type w;
+    typename Sink::template Pre<VEC, NP> pre;
     float acc[NP][VEC];
-    float m_old = 0.f;
-    int slot = 0;
-    if (wave == 0) {
-      if constexpr (Sink::kApply) {
-        load_w_row<VEC, NP>(sink.weight + (int64_t)id * dim, lane, pieces, w);
-        m_old = sink.momentum1[id];
-      } else {
-        slot = sink.rank[c1 - 1] - 1;
-      }
-    }
+    if (wave == 0) sink.template prefetch<VEC, NP>(pre, id, c1 - 1, lane, pieces, dim);
 #pragma unroll
     for (int j = 0; j < NP; ++j)
 #pragma unroll
@@ -470,10 +621,7 @@ __global__ __launch_bounds__(kCombineWaves * 64) void adagrad_combine_kernel(con
         load_f32_row<VEC, NP>(shares + (int64_t)s * dim, lane, pieces, v);
         add_row<VEC, NP>(acc, v, lane, pieces);
       }
-      if constexpr (Sink::kApply)
-        finish_apply<VEC, NP>(acc, w, m_old, lane, pieces, dim, id, sink);
-      else
-        emit_segment<VEC, NP>(acc, lane, pieces, dim, sink, id, slot);
+      sink.template finish<VEC, NP>(acc, pre, id, lane, pieces, dim);
     }
     __syncthreads();                                         // the shares are read before the next segment's are written
   }
@@ -637,12 +785,12 @@ static int opt_launch_chunk(const OptArgs& a, const Sink& sink, const char* what
   constexpr int VEC = 16 / (int)sizeof(T);
   const int64_t chunks = (a.n + kChunk - 1) / kChunk;
   const int64_t blocks = (chunks + kOptWaves - 1) / kOptWaves;
-  hipLaunchKernelGGL((adagrad_chunk_kernel<T, NP, U, kChunk, Sink>), dim3((unsigned)(blocks < kOptMaxBlocks ? blocks : kOptMaxBlocks)),
+  hipLaunchKernelGGL((optim_chunk_kernel<T, NP, U, kChunk, Sink>), dim3((unsigned)(blocks < kOptMaxBlocks ? blocks : kOptMaxBlocks)),
                      dim3(kOptWaves * 64), 0, a.st, (const T*)a.g, a.perm, a.sorted_idx, a.n, a.dim, a.partials, sink);
   if (int rc = check_launch(what)) return rc;
   if (chunks < 2) return HSTU_OK;                                          // one chunk: nothing can leave it
   const size_t lds = (size_t)(kCombineWaves - 1) * a.dim * sizeof(float);  // at most 56 KiB
-  hipLaunchKernelGGL((adagrad_combine_kernel<VEC, NP, kChunk, Sink>), dim3((unsigned)(chunks - 1 < kOptMaxBlocks ? chunks - 1 : kOptMaxBlocks)),
+  hipLaunchKernelGGL((optim_combine_kernel<VEC, NP, kChunk, Sink>), dim3((unsigned)(chunks - 1 < kOptMaxBlocks ? chunks - 1 : kOptMaxBlocks)),
                      dim3(kCombineWaves * 64), lds, a.st, a.sorted_idx, a.n, a.dim, a.partials, sink);
   return check_launch(what);
 }
@@ -712,43 +860,124 @@ int hstu_embedding_rowwise_adagrad_workspace_bytes(int64_t n, int32_t table_rows
   return HSTU_OK;
 }
 
-// the update behind the entry points; max_row_bytes: the widest dout row the entry point takes; weight_dtype: fp32, or a
-// 16-bit table written back by stochastic rounding with `seed`
-static int rowwise_adagrad_impl(const char* what, int max_row_bytes, const void* dout, const int32_t* idx, int64_t n, int32_t dim,
-                                int32_t table_rows, void* weight, int weight_dtype, float* momentum1, float lr, float eps, uint64_t seed,
-                                void* workspace, int64_t workspace_bytes, int dtype, void* stream) {
-  if (!weight || !momentum1 || table_rows <= 0 || dim <= 0)
-    return set_error(HSTU_EINVAL, "%s: weight and momentum1 must be non-NULL, sizes positive", what);
-  if (!is_float_dtype(dtype)) return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32", what);
-  if (weight_dtype != HSTU_DTYPE_F32 && dim % 8)
-    return set_error(HSTU_EINVAL, "%s: 16-bit table rows must be 16-byte multiples (dim %d is not a multiple of 8)", what, dim);
-  const int es = dtype_bytes(dtype);
-  if (dim > kOptMaxDim)                             // before any product with dim: dim * es must not wrap
-    return set_error(HSTU_EUNSUPPORTED, "%s: rows of %d columns > %d", what, dim, kOptMaxDim);
-  if ((dim * es) % 16 || ((uintptr_t)dout & 15) || ((uintptr_t)weight & 15))
+// What every update's entry point takes, and the part they share: the checks and the sort.  max_row_bytes: the widest dout row
+// the entry point takes; weight_dtype: fp32, or a 16-bit table written back by stochastic rounding; state_ok: the optimizer's
+// state tensors (named in `tensors` with the weight) are there.  *go is false when there is nothing to launch.
+struct SparseCall {
+  const char* what;
+  int max_row_bytes;
+  const void* dout;
+  const int32_t* idx;
+  int64_t n;
+  int32_t dim, table_rows;
+  void* weight;
+  int weight_dtype;
+  void* workspace;
+  int64_t workspace_bytes;
+  int dtype;
+  void* stream;
+};
+
+static int sparse_update_begin(const SparseCall& c, bool state_ok, const char* tensors, OptArgs* a, bool* go) {
+  const char* what = c.what;
+  *go = false;
+  if (!c.weight || !state_ok || c.table_rows <= 0 || c.dim <= 0)
+    return set_error(HSTU_EINVAL, "%s: %s must be non-NULL, sizes positive", what, tensors);
+  if (!is_float_dtype(c.dtype)) return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32", what);
+  if (c.weight_dtype != HSTU_DTYPE_F32 && c.dim % 8)
+    return set_error(HSTU_EINVAL, "%s: 16-bit table rows must be 16-byte multiples (dim %d is not a multiple of 8)", what, c.dim);
+  const int es = dtype_bytes(c.dtype);
+  if (c.dim > kOptMaxDim)                           // before any product with dim: dim * es must not wrap
+    return set_error(HSTU_EUNSUPPORTED, "%s: rows of %d columns > %d", what, c.dim, kOptMaxDim);
+  if ((c.dim * es) % 16 || ((uintptr_t)c.dout & 15) || ((uintptr_t)c.weight & 15))
     return set_error(HSTU_EINVAL, "%s: rows must be 16-byte multiples and 16-byte aligned", what);
-  if (dim * es > max_row_bytes)
-    return set_error(HSTU_EUNSUPPORTED, "%s: rows of %d bytes > %d", what, dim * es, max_row_bytes);
-  if (n < 0 || n > 0x7fffffffLL) return set_error(HSTU_EINVAL, "%s: n out of range", what);
-  if (n == 0) return HSTU_OK;
-  if (!dout || !idx || !workspace) return set_error(HSTU_EINVAL, "%s: NULL input", what);
-  const OptLayout l = opt_layout(n, table_rows);
-  if (workspace_bytes < (int64_t)l.total || ((uintptr_t)workspace & 255))
+  if (c.dim * es > c.max_row_bytes)
+    return set_error(HSTU_EUNSUPPORTED, "%s: rows of %d bytes > %d", what, c.dim * es, c.max_row_bytes);
+  if (c.n < 0 || c.n > 0x7fffffffLL) return set_error(HSTU_EINVAL, "%s: n out of range", what);
+  if (c.n == 0) return HSTU_OK;
+  if (!c.dout || !c.idx || !c.workspace) return set_error(HSTU_EINVAL, "%s: NULL input", what);
+  const OptLayout l = opt_layout(c.n, c.table_rows);
+  if (c.workspace_bytes < (int64_t)l.total || ((uintptr_t)c.workspace & 255))
     return set_error(HSTU_EINVAL, "%s: workspace too small or not 256-byte aligned (hstu_embedding_rowwise_adagrad_workspace_bytes)",
                      what);
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
+  hipStream_t st = (hipStream_t)c.stream;
+  char* ws = (char*)c.workspace;
   int32_t* sorted_idx = (int32_t*)ws;
   int32_t* perm = (int32_t*)(ws + l.part);
   float* partials = (float*)(ws + l.partials_off);
   size_t temp = l.temp_bytes;
-  hipError_t e = sort_indices(ws + l.temp_off, temp, idx, sorted_idx, perm, n, table_rows, st);
+  hipError_t e = sort_indices(ws + l.temp_off, temp, c.idx, sorted_idx, perm, c.n, c.table_rows, st);
   if (e != hipSuccess) return set_error(HSTU_ELAUNCH, "%s: sort failed: %s", what, hipGetErrorString(e));
-  const OptArgs a{dout, perm, sorted_idx, n, dim, partials, st};
+  *a = OptArgs{c.dout, perm, sorted_idx, c.n, c.dim, partials, st};
+  *go = true;
+  return HSTU_OK;
+}
+
+// 16-bit gradient rows of up to 4 KiB, fp32 ones (the coalesced lists) of up to 8 KiB: dim <= 2048 either way
+static int both_row_domains(int dtype) { return dtype == HSTU_DTYPE_F32 ? kOptMaxDim * (int)sizeof(float) : kOptMaxPieces * 64 * 16; }
+
+static int rowwise_adagrad_impl(const char* what, int max_row_bytes, const void* dout, const int32_t* idx, int64_t n, int32_t dim,
+                                int32_t table_rows, void* weight, int weight_dtype, float* momentum1, float lr, float eps, uint64_t seed,
+                                void* workspace, int64_t workspace_bytes, int dtype, void* stream) {
+  const SparseCall c{what, max_row_bytes, dout, idx, n, dim, table_rows, weight, weight_dtype, workspace, workspace_bytes, dtype, stream};
+  OptArgs a;
+  bool go;
+  if (int rc = sparse_update_begin(c, momentum1 != nullptr, "weight and momentum1", &a, &go)) return rc;
+  if (!go) return HSTU_OK;
   switch (weight_dtype) {
     case HSTU_DTYPE_F16: return opt_dispatch_dtype(dtype, a, ApplySink16<f16_t>{(f16_t*)weight, momentum1, lr, eps, seed}, what);
     case HSTU_DTYPE_BF16: return opt_dispatch_dtype(dtype, a, ApplySink16<bf16_t>{(bf16_t*)weight, momentum1, lr, eps, seed}, what);
     default: return opt_dispatch_dtype(dtype, a, ApplySink{(float*)weight, momentum1, lr, eps}, what);
+  }
+}
+
+static bool is_table_dtype(int weight_dtype) {
+  return weight_dtype == HSTU_DTYPE_F32 || weight_dtype == HSTU_DTYPE_F16 || weight_dtype == HSTU_DTYPE_BF16;
+}
+
+int hstu_embedding_sparse_sgd(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows, void* weight,
+                              int weight_dtype, float lr, uint64_t seed, void* workspace, int64_t workspace_bytes, int dtype,
+                              void* stream) {
+  const char* what = "hstu_embedding_sparse_sgd";
+  if (!is_table_dtype(weight_dtype)) return set_error(HSTU_EINVAL, "%s: weight_dtype must be fp32, fp16 or bf16", what);
+  const SparseCall c{what, both_row_domains(dtype), dout, idx, n, dim, table_rows, weight, weight_dtype, workspace, workspace_bytes,
+                     dtype, stream};
+  OptArgs a;
+  bool go;
+  if (int rc = sparse_update_begin(c, true, "weight", &a, &go)) return rc;
+  if (!go) return HSTU_OK;
+  switch (weight_dtype) {
+    case HSTU_DTYPE_F16: return opt_dispatch_dtype(dtype, a, SgdSink<f16_t>{(f16_t*)weight, lr, seed}, what);
+    case HSTU_DTYPE_BF16: return opt_dispatch_dtype(dtype, a, SgdSink<bf16_t>{(bf16_t*)weight, lr, seed}, what);
+    default: return opt_dispatch_dtype(dtype, a, SgdSink<float>{(float*)weight, lr, 0}, what);
+  }
+}
+
+int hstu_embedding_sparse_adam(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows, void* weight,
+                               int weight_dtype, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
+                               int64_t step, uint64_t seed, void* workspace, int64_t workspace_bytes, int dtype, void* stream) {
+  const char* what = "hstu_embedding_sparse_adam";
+  if (!is_table_dtype(weight_dtype)) return set_error(HSTU_EINVAL, "%s: weight_dtype must be fp32, fp16 or bf16", what);
+  if (!(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f))      // false for NaN
+    return set_error(HSTU_EINVAL, "%s: beta1 and beta2 must lie in [0, 1), got %g and %g", what, (double)beta1, (double)beta2);
+  if (step < 0) return set_error(HSTU_EINVAL, "%s: step must be >= 0 (the updates applied before this one)", what);
+  if (((uintptr_t)exp_avg & 15) || ((uintptr_t)exp_avg_sq & 15))
+    return set_error(HSTU_EINVAL, "%s: exp_avg and exp_avg_sq must be 16-byte aligned", what);
+  const SparseCall c{what, both_row_domains(dtype), dout, idx, n, dim, table_rows, weight, weight_dtype, workspace, workspace_bytes,
+                     dtype, stream};
+  OptArgs a;
+  bool go;
+  if (int rc = sparse_update_begin(c, exp_avg && exp_avg_sq, "weight, exp_avg and exp_avg_sq", &a, &go)) return rc;
+  if (!go) return HSTU_OK;
+  // t = step + 1; the bias corrections in double, handed to the kernels as floats.  fp32 state rows of a dim that is a multiple
+  // of 4 are 16-byte multiples (dim * es % 16 == 0 gives dim % 4 == 0 for every dout dtype)
+  const double t = (double)step + 1.0;
+  const float bc1 = (float)(1.0 - pow((double)beta1, t)), bc2 = (float)(1.0 - pow((double)beta2, t));
+  const AdamCoef k{beta1, (float)(1.0 - (double)beta1), beta2, (float)(1.0 - (double)beta2), lr / bc1, sqrtf(bc2), eps};
+  switch (weight_dtype) {
+    case HSTU_DTYPE_F16: return opt_dispatch_dtype(dtype, a, AdamSink<f16_t>{(f16_t*)weight, exp_avg, exp_avg_sq, k, seed}, what);
+    case HSTU_DTYPE_BF16: return opt_dispatch_dtype(dtype, a, AdamSink<bf16_t>{(bf16_t*)weight, exp_avg, exp_avg_sq, k, seed}, what);
+    default: return opt_dispatch_dtype(dtype, a, AdamSink<float>{(float*)weight, exp_avg, exp_avg_sq, k, 0}, what);
   }
 }
 
@@ -772,9 +1001,7 @@ int hstu_embedding_rowwise_adagrad_lowp(const void* dout, const int32_t* idx, in
   const char* what = "hstu_embedding_rowwise_adagrad_lowp";
   if (weight_dtype != HSTU_DTYPE_F16 && weight_dtype != HSTU_DTYPE_BF16)
     return set_error(HSTU_EINVAL, "%s: weight_dtype must be fp16 or bf16 (fp32 tables: hstu_embedding_rowwise_adagrad)", what);
-  // 16-bit gradient rows of up to 4 KiB, fp32 ones (the coalesced lists) of up to 8 KiB: dim <= 2048 either way
-  const int max_row_bytes = dtype == HSTU_DTYPE_F32 ? kOptMaxDim * (int)sizeof(float) : kOptMaxPieces * 64 * 16;
-  return rowwise_adagrad_impl(what, max_row_bytes, dout, idx, n, dim, table_rows, weight, weight_dtype, momentum1, lr, eps, seed, workspace,
+  return rowwise_adagrad_impl(what, both_row_domains(dtype), dout, idx, n, dim, table_rows, weight, weight_dtype, momentum1, lr, eps, seed, workspace,
                               workspace_bytes, dtype, stream);
 }
 

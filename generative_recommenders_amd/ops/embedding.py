@@ -50,6 +50,48 @@ class RowWiseAdagradConfig:
         self.seed = int(seed)
 
 
+class SparseSGDConfig:
+    """``RowWiseAdagradConfig``'s fields without ``eps`` for a table trained by in-backward sparse SGD (``sparse_sgd_update_``;
+    no momentum, no weight decay, no state)."""
+
+    def __init__(self, lr: float, rows_dtype: Optional[torch.dtype] = None, replicated: bool = False, process_group: Any = None,
+                 average: bool = True, seed: int = 0) -> None:
+        self.lr = float(lr)
+        self.rows_dtype = rows_dtype
+        self.replicated = bool(replicated)
+        self.process_group = process_group
+        self.average = bool(average)
+        self.seed = int(seed)
+
+
+def check_betas(betas: Any) -> Tuple[float, float]:
+    """``(beta1, beta2)`` as floats; refused outside [0, 1) (NaN included)"""
+    try:
+        beta1, beta2 = (float(b) for b in betas)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"betas must be a pair of numbers, got {betas!r}") from None
+    if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0):
+        raise RuntimeError(f"betas must lie in [0, 1), got {(beta1, beta2)}")
+    return beta1, beta2
+
+
+class SparseAdamConfig:
+    """``RowWiseAdagradConfig``'s fields plus ``betas`` for a table trained by in-backward sparse Adam (``sparse_adam_update_``).
+    A 16-bit table's rounding seed is ``update_seed(seed, step)`` with Adam's own step count."""
+
+    def __init__(self, lr: float, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 rows_dtype: Optional[torch.dtype] = None, replicated: bool = False, process_group: Any = None,
+                 average: bool = True, seed: int = 0) -> None:
+        self.lr = float(lr)
+        self.betas = check_betas(betas)
+        self.eps = float(eps)
+        self.rows_dtype = rows_dtype
+        self.replicated = bool(replicated)
+        self.process_group = process_group
+        self.average = bool(average)
+        self.seed = int(seed)
+
+
 _M64 = (1 << 64) - 1
 
 
@@ -149,6 +191,85 @@ def rowwise_adagrad_update_(weight: torch.Tensor, momentum1: torch.Tensor, idx: 
             ws.data_ptr(), ws.numel(), L.torch_dtype_code(dout.dtype), L.current_stream_ptr(weight.device)))
 
 
+def _sparse_update_args(fn: str, weight: torch.Tensor, state: Dict[str, torch.Tensor], idx: torch.Tensor, dout: torch.Tensor,
+                        seed: Optional[int]) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, int]]:
+    """the checks of ``rowwise_adagrad_update_`` for an update whose state tensors have the weight's shape in fp32;
+    -> (dout, idx, workspace, seed as the entry point takes it), or None when the batch is empty"""
+    tensors = [("weight", weight)] + list(state.items()) + [("idx", idx), ("dout", dout)]
+    for name, t in tensors:
+        L.require_gpu_tensor(t, name)
+    if any(t.device != weight.device for _, t in tensors):
+        raise RuntimeError(f"{fn}: {', '.join(n for n, _ in tensors)} must be on one device, got "
+                           f"{', '.join(str(t.device) for _, t in tensors)}")
+    lowp = weight.dtype in _LOWP
+    if not lowp and weight.dtype != torch.float32:
+        raise RuntimeError(f"{fn}: weight must be float32, float16 or bfloat16, got {weight.dtype}")
+    if lowp and seed is None:
+        raise RuntimeError(f"{fn}: a {weight.dtype} weight is written back by stochastic rounding and needs a seed")
+    if not lowp and seed is not None:
+        raise RuntimeError(f"{fn}: seed is the stochastic rounding's and a float32 weight is not rounded; pass none")
+    if weight.dim() != 2 or not weight.is_contiguous():
+        raise RuntimeError(f"{fn}: weight must be a contiguous (rows, dim) tensor (it is updated in place), got {tuple(weight.shape)}")
+    for name, t in state.items():
+        if t.dtype != torch.float32 or t.shape != weight.shape or not t.is_contiguous():
+            raise RuntimeError(f"{fn}: {name} must be a contiguous float32 tensor of the weight's shape {tuple(weight.shape)}, got "
+                               f"{t.dtype} {tuple(t.shape)}")
+    rows, dim = weight.shape
+    if lowp and dim % 8:
+        raise RuntimeError(f"{fn}: rows of a {weight.dtype} weight must be 16-byte multiples (dim {dim} is not a multiple of 8)")
+    if dout.dim() != 2 or dout.shape[1] != dim or idx.dim() != 1 or idx.shape[0] != dout.shape[0]:
+        raise RuntimeError(f"{fn}: idx (n) and dout (n, {dim}), got {tuple(idx.shape)} and {tuple(dout.shape)}")
+    n = idx.shape[0]
+    if n == 0:
+        return None
+    need = C.c_int64(0)
+    L.check(L.lib().hstu_embedding_rowwise_adagrad_workspace_bytes(n, rows, C.byref(need)))
+    ws = torch.empty(max(need.value, 256), dtype=torch.uint8, device=weight.device)
+    return dout.detach().contiguous(), idx.detach().to(torch.int32).contiguous(), ws, (int(seed) & _M64) if lowp else 0
+
+
+def sparse_sgd_update_(weight: torch.Tensor, idx: torch.Tensor, dout: torch.Tensor, lr: float, seed: Optional[int] = None) -> None:
+    """in place: ``weight[r] -= lr * G[r]`` for every row r among the ids ``idx`` (n), ``G[r]`` the fp32 sum of its gradient rows
+    ``dout`` (n, dim; bf16, fp16 or fp32) -- the sum ``rowwise_adagrad_update_`` forms, addition for addition.  SGD without
+    momentum or weight decay: there is no state.  ``weight`` and ``seed`` as for ``rowwise_adagrad_update_`` (a 16-bit weight is
+    updated in fp32 and written back by stochastic rounding with ``seed``)."""
+    args = _sparse_update_args("sparse_sgd_update_", weight, {}, idx, dout, seed)
+    if args is None:
+        return
+    dout, idx, ws, seed = args
+    with torch.cuda.device(weight.device):
+        L.check(L.lib().hstu_embedding_sparse_sgd(
+            dout.data_ptr(), idx.data_ptr(), idx.shape[0], weight.shape[1], weight.shape[0], weight.data_ptr(),
+            L.torch_dtype_code(weight.dtype), float(lr), seed, ws.data_ptr(), ws.numel(), L.torch_dtype_code(dout.dtype),
+            L.current_stream_ptr(weight.device)))
+
+
+def sparse_adam_update_(weight: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, idx: torch.Tensor, dout: torch.Tensor,
+                        lr: float, betas: Tuple[float, float], eps: float, step: int, seed: Optional[int] = None) -> None:
+    """in place, for every row r among the ids ``idx`` (n) and only those, with ``G[r]`` as in ``sparse_sgd_update_`` and
+    ``t = step + 1`` (``step``: the updates applied to the table before this one):
+
+        exp_avg[r]    = beta1 * exp_avg[r]    + (1 - beta1) * G[r]
+        exp_avg_sq[r] = beta2 * exp_avg_sq[r] + (1 - beta2) * G[r]^2
+        weight[r]    -= lr / (1 - beta1^t) * exp_avg[r] / (sqrt(exp_avg_sq[r]) / sqrt(1 - beta2^t) + eps)
+
+    ``torch.optim.Adam``'s arithmetic (``amsgrad=False``, ``weight_decay=0``) applied lazily: rows outside the batch do not
+    decay, as in fbgemm's in-backward Adam and ``torch.optim.SparseAdam`` (whose eps placement is NOT used).  ``exp_avg`` and
+    ``exp_avg_sq`` are (rows, dim) fp32 whatever the weight's dtype; ``weight`` and ``seed`` as for ``rowwise_adagrad_update_``."""
+    beta1, beta2 = check_betas(betas)
+    if int(step) < 0:
+        raise RuntimeError(f"sparse_adam_update_: step counts the updates applied so far and must be >= 0, got {step}")
+    args = _sparse_update_args("sparse_adam_update_", weight, {"exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq}, idx, dout, seed)
+    if args is None:
+        return
+    dout, idx, ws, seed = args
+    with torch.cuda.device(weight.device):
+        L.check(L.lib().hstu_embedding_sparse_adam(
+            dout.data_ptr(), idx.data_ptr(), idx.shape[0], weight.shape[1], weight.shape[0], weight.data_ptr(),
+            L.torch_dtype_code(weight.dtype), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), float(lr), beta1, beta2, float(eps), int(step),
+            seed, ws.data_ptr(), ws.numel(), L.torch_dtype_code(dout.dtype), L.current_stream_ptr(weight.device)))
+
+
 def coalesce_row_gradients(idx: torch.Tensor, dout: torch.Tensor, table_rows: int,
                            scale: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``(rows, G, count)``: the distinct ids of ``idx`` (n) in ascending order, ``G[s] = scale * (sum of the dout rows whose id
@@ -205,28 +326,36 @@ def exchange_row_gradients(rows: torch.Tensor, G: torch.Tensor, count: torch.Ten
     return gathered(rows), gathered(G)
 
 
-def _fused_tables(collection: Any) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
-    """table name -> (weight, momentum1) of the tables an ``EmbeddingCollection`` (or the model that holds one) trains in backward"""
+_STATE_KEYS = ("momentum1", "exp_avg", "exp_avg_sq")
+_STEP_KEYS = ("rounding_step", "step")
+
+
+def _fused_tables(collection: Any) -> Dict[str, Tuple[torch.Tensor, ...]]:
+    """table name -> (weight, its state tensors: momentum1, or exp_avg and exp_avg_sq, or none for SGD) of the tables an
+    ``EmbeddingCollection`` (or the model that holds one) trains in backward"""
     collection = getattr(collection, "_embedding_collection", collection)
     state = collection.fused_optimizer_state_dict()
-    return {t: (collection.embeddings[t].weight.detach(), state[f"{t}.momentum1"].detach()) for t in collection._fused}
+    return {t: (collection.embeddings[t].weight.detach(),) + tuple(state[f"{t}.{k}"].detach() for k in _STATE_KEYS if f"{t}.{k}" in state)
+            for t in collection._fused}
 
 
 def _fused_steps(collection: Any) -> Dict[str, torch.Tensor]:
-    """table name -> the int64 count of applied updates of every 16-bit fused table (``"{table}.rounding_step"``)"""
+    """table name -> the int64 count of applied updates of every fused table that keeps one: ``"{table}.rounding_step"`` of a
+    16-bit Adagrad or SGD table, ``"{table}.step"`` of an Adam table"""
     collection = getattr(collection, "_embedding_collection", collection)
     state = collection.fused_optimizer_state_dict()
-    return {t: state[f"{t}.rounding_step"] for t in collection._fused if f"{t}.rounding_step" in state}
+    return {t: state[f"{t}.{k}"] for t in collection._fused for k in _STEP_KEYS if f"{t}.{k}" in state}
 
 
 def fused_tables_checksum(collection: Any) -> Dict[str, int]:
     """Per fused table one exact integer: the wrapping int64 sum of the fp32 bit patterns (read as int32) of ``weight`` and of
-    ``momentum1``.  Equal tables give equal sums; one flipped bit changes the sum.  A 16-bit table's weight is summed
-    through an int16 view, and its count of applied updates is added."""
+    its state (``momentum1``; ``exp_avg`` and ``exp_avg_sq`` of an Adam table).  Equal tables give equal sums; one flipped bit
+    changes the sum.  A 16-bit table's weight is summed through an int16 view, and a table's count of applied updates, where it
+    keeps one, is added."""
     bits = lambda t: int(t.contiguous().view(torch.int16 if t.dtype in _LOWP else torch.int32).sum(dtype=torch.int64))
     wrap = lambda v: (v + (1 << 63)) % (1 << 64) - (1 << 63)
     steps = _fused_steps(collection)
-    return {t: wrap(bits(w) + bits(m) + (int(steps[t]) if t in steps else 0)) for t, (w, m) in _fused_tables(collection).items()}
+    return {t: wrap(sum(bits(x) for x in ts) + (int(steps[t]) if t in steps else 0)) for t, ts in _fused_tables(collection).items()}
 
 
 def assert_fused_tables_in_sync(collection: Any, group: Any = None) -> None:
@@ -252,15 +381,16 @@ def assert_fused_tables_in_sync(collection: Any, group: Any = None) -> None:
 
 
 def broadcast_fused_tables(collection: Any, src: int = 0, group: Any = None) -> None:
-    """Step 0 of replicated training: every rank's fused tables and their ``momentum1`` become rank ``src``'s, and so does a
-    16-bit table's count of applied updates (a collective; staged through host memory on backends other than ``nccl``)."""
+    """Step 0 of replicated training: every rank's fused tables and their state (``momentum1``, ``exp_avg``, ``exp_avg_sq``) become
+    rank ``src``'s, and so does a table's count of applied updates (a collective; staged through host memory on backends
+    other than ``nccl``)."""
     dist = torch.distributed
     on_device = dist.get_backend(group) == "nccl"
     steps = _fused_steps(collection)
     with torch.no_grad():
-        for table, (weight, momentum1) in _fused_tables(collection).items():
-            for t in (weight, momentum1) + ((steps[table],) if table in steps else ()):
-                buf = t.to(weight.device) if on_device else t.cpu()
+        for table, tensors in _fused_tables(collection).items():
+            for t in tensors + ((steps[table],) if table in steps else ()):
+                buf = t.to(tensors[0].device) if on_device else t.cpu()
                 dist.broadcast(buf, src=src, group=group)
                 if buf is not t:
                     t.copy_(buf)
@@ -274,28 +404,42 @@ def _refuse_replicated_tables() -> None:
             f"would diverge, and sharded tables are out of scope (world size {dist.get_world_size()})")
 
 
+def _apply_update(weight: torch.Tensor, state: Any, idx: torch.Tensor, g: torch.Tensor, cfg: Any, step: Any, seed: Optional[int]) -> None:
+    """the update of ``cfg``'s optimizer; ``state``: momentum1 (Adagrad), (exp_avg, exp_avg_sq) (Adam), None (SGD)"""
+    rounding = {} if seed is None else {"seed": seed}           # fp32 tables: the call is the one it was
+    if isinstance(cfg, SparseAdamConfig):
+        sparse_adam_update_(weight, state[0], state[1], idx, g, cfg.lr, cfg.betas, cfg.eps, int(step), **rounding)
+    elif isinstance(cfg, SparseSGDConfig):
+        sparse_sgd_update_(weight, idx, g, cfg.lr, **rounding)
+    else:
+        rowwise_adagrad_update_(weight, state, idx, g, cfg.lr, cfg.eps, **rounding)
+
+
 class _GatherRowsFusedFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, momentum1, idx, cfg, rows_dtype, step=None):
         ctx.save_for_backward(idx)
         ctx.table = (weight, momentum1, cfg)        # the parameter and its state themselves: the update is in place
-        ctx.step = step                             # a 16-bit table's count of applied updates (int64, in place too)
+        ctx.step = step                             # the table's count of applied updates (int64, in place too), where it keeps one
         rows = weight.index_select(0, idx)
         return rows if rows_dtype is None else rows.to(rows_dtype)
 
     @staticmethod
     def backward(ctx, g):
         (idx,) = ctx.saved_tensors
-        weight, momentum1, cfg = ctx.table
+        weight, state, cfg = ctx.table
         step, seed = ctx.step, None
         none = (None,) * (5 if step is None else 6)
-        if weight.dtype in _LOWP:
+        lowp, adam = weight.dtype in _LOWP, isinstance(cfg, SparseAdamConfig)
+        counts = lowp or adam                       # Adam's bias correction and a 16-bit table's rounding seed need the count
+        if counts:
             if step is None:
-                raise RuntimeError(f"a {weight.dtype} table trained in backward needs its step counter (gather_rows_fused's step)")
+                raise RuntimeError(f"a {weight.dtype} table trained in backward" + (" by Adam" if adam else "")
+                                   + " needs its step counter (gather_rows_fused's step)")
             if idx.numel() == 0 and not getattr(cfg, "replicated", False):
                 return none                         # an empty batch applies nothing and does not count
-            seed = update_seed(getattr(cfg, "seed", 0), int(step))
-        rounding = {} if seed is None else {"seed": seed}       # fp32 tables: the call is the one it was
+            if lowp:
+                seed = update_seed(getattr(cfg, "seed", 0), int(step))
         dist = torch.distributed
         if getattr(cfg, "replicated", False) and dist.is_available() and dist.is_initialized():
             # every rank applies every rank's row gradients, in rank order: the copies of the table keep equal bits.  The
@@ -305,24 +449,26 @@ class _GatherRowsFusedFunction(torch.autograd.Function):
             with torch.no_grad():
                 rows, G, count = coalesce_row_gradients(idx, g, weight.shape[0], scale)
                 rows_all, G_all = exchange_row_gradients(rows, G, count, group)
-                rowwise_adagrad_update_(weight, momentum1, rows_all, G_all, cfg.lr, cfg.eps, **rounding)
-                if seed is not None and rows_all.numel() > 0:      # the same list on every rank: the same count
+                _apply_update(weight, state, rows_all, G_all, cfg, step, seed)
+                if counts and rows_all.numel() > 0:             # the same list on every rank: the same count
                     step += 1
             return none
         _refuse_replicated_tables()
         with torch.no_grad():
-            rowwise_adagrad_update_(weight, momentum1, idx, g, cfg.lr, cfg.eps, **rounding)
-            if seed is not None:
+            _apply_update(weight, state, idx, g, cfg, step, seed)
+            if counts:
                 step += 1
         return none
 
 
-def gather_rows_fused(weight: torch.Tensor, momentum1: torch.Tensor, idx: torch.Tensor, cfg: Any,
+def gather_rows_fused(weight: torch.Tensor, momentum1: Any, idx: torch.Tensor, cfg: Any,
                       rows_dtype: Optional[torch.dtype] = None, step: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``weight[idx]`` (cast to ``rows_dtype`` when given) whose backward applies the row-wise Adagrad step of ``cfg`` (``lr``,
-    ``eps``) to ``weight`` and ``momentum1`` in place and hands autograd no gradient for the table: ``weight.grad`` stays None.
-    A float16 / bfloat16 ``weight`` needs ``step``, its int64 count of applied updates: backward rounds with
-    ``update_seed(cfg.seed, step)`` and adds 1 to it (an empty batch applies nothing and does not count)."""
+    """``weight[idx]`` (cast to ``rows_dtype`` when given) whose backward applies the optimizer step of ``cfg`` to ``weight`` and
+    its state in place and hands autograd no gradient for the table: ``weight.grad`` stays None.  ``cfg`` picks the update: a
+    ``SparseAdamConfig`` (``momentum1`` is then the pair ``(exp_avg, exp_avg_sq)``), a ``SparseSGDConfig`` (``momentum1`` is None),
+    anything else with ``lr`` and ``eps`` the row-wise Adagrad step on ``momentum1``.  An Adam table and every float16 / bfloat16
+    ``weight`` need ``step``, the table's int64 count of applied updates: backward takes Adam's ``t = step + 1`` and the rounding
+    seed ``update_seed(cfg.seed, step)`` from it and adds 1 to it (an empty batch applies nothing and does not count)."""
     if step is None:
         return _GatherRowsFusedFunction.apply(weight, momentum1, idx, cfg, rows_dtype)
     return _GatherRowsFusedFunction.apply(weight, momentum1, idx, cfg, rows_dtype, step)

@@ -448,6 +448,32 @@ int hstu_embedding_rowwise_adagrad_lowp(const void* dout, const int32_t* idx, in
  * and both are 16-byte aligned); row_ids (n) int32 or NULL; n == 0 touches nothing. */
 int hstu_stochastic_round(const float* src, const int32_t* row_ids, void* dst, int64_t n, int32_t dim, int dst_dtype,
                           uint64_t seed, void* stream);
+/* In-backward sparse SGD and sparse Adam on the same segment walk (the other two choices of the reference's
+ * sparse_optimizer_factory_and_class, dlrm_v3/train/utils.py:169-206; weight_decay = 0, SGD momentum = 0, no amsgrad).
+ * G[r, :] is the sum above, addition for addition.  For every table row r that occurs in idx, and only for those rows:
+ *   SGD:   weight[r, :] -= lr * G[r, :]                                          (no state)
+ *   Adam:  exp_avg[r, :]    = beta1 * exp_avg[r, :]    + (1 - beta1) * G[r, :]
+ *          exp_avg_sq[r, :] = beta2 * exp_avg_sq[r, :] + (1 - beta2) * G[r, :]^2
+ *          weight[r, :] -= (lr / bc1) * exp_avg[r, :] / (sqrt(exp_avg_sq[r, :]) / sqrt(bc2) + eps)
+ *          with t = step + 1, bc1 = 1 - beta1^t, bc2 = 1 - beta2^t formed on the host in double and rounded to fp32:
+ *          torch.optim.Adam's arithmetic (amsgrad off), applied LAZILY -- rows outside the batch do not decay (what
+ *          fbgemm's in-backward ADAM and torch.optim.SparseAdam do; eps is placed as in torch.optim.Adam, not SparseAdam).
+ * in place; every other row of weight and of exp_avg / exp_avg_sq (both (table_rows, dim) fp32) keeps its bits.  `step` >= 0
+ * is the caller's count of updates applied before this one; 0 <= beta1, beta2 < 1.  weight (table_rows, dim) in
+ * `weight_dtype`: HSTU_DTYPE_F32, or HSTU_DTYPE_F16 / HSTU_DTYPE_BF16 (dim a multiple of 8) -- then the row is widened, updated by
+ * exactly the fp32 table's arithmetic (the same fp32 row, exp_avg and exp_avg_sq bit for bit) and written back by the
+ * stochastic rounding of hstu_embedding_rowwise_adagrad_lowp with `seed`; `seed` is read only for 16-bit tables.  dout
+ * (n, dim) in `dtype`: bf16 / fp16 rows of at most 4 KiB, or fp32 rows of at most 8 KiB (dim <= 2048), so one entry also takes
+ * the coalesced lists of replicated tables.  Alignment, n, idx and the guarantees (no float atomics, no table-sized
+ * temporary, bit-identical from run to run) are hstu_embedding_rowwise_adagrad's.  Workspace:
+ * hstu_embedding_rowwise_adagrad_workspace_bytes -- the layout is the same. */
+int hstu_embedding_sparse_sgd(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows, void* weight,
+                              int weight_dtype, float lr, uint64_t seed, void* workspace, int64_t workspace_bytes, int dtype,
+                              void* stream);
+int hstu_embedding_sparse_adam(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows, void* weight,
+                               int weight_dtype, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
+                               float eps, int64_t step, uint64_t seed, void* workspace, int64_t workspace_bytes, int dtype,
+                               void* stream);
 /* The first half of that update alone, for data-parallel ranks that exchange their row gradients before applying them:
  * the batch's (idx, dout) coalesced to one fp32 row per distinct id.
  *   rows[s]  = the s-th smallest distinct id of idx (ascending), s < u = *count

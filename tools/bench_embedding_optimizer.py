@@ -24,9 +24,16 @@ distinct ids, beside the raw alternative n / W * (4 + es * dim); the exchange it
 stochastic rounding) against the fp32 table's, the two alternating in one process on the same ids and gradient rows.  The
 16-bit table's algorithmic bytes: n * dim * sizeof(dout) + unique * (2 * dim * 2 + 8).
 
+--optimizer adam | sgd times the in-backward sparse Adam / SGD the same way (same shapes, same method).  Their dense path is
+``_table_grad`` followed by ``torch.optim.Adam`` / ``torch.optim.SGD`` over the whole table (dense Adam also decays the
+moments of rows outside the batch, so only the first step from zero state is compared).  Algorithmic bytes: Adam
+n * dim * sizeof(dout) + unique * (6 * dim * 4 + 8) -- the table row and both moment rows read and written --, SGD
+n * dim * sizeof(dout) + unique * 2 * dim * 4.
+
     python tools/bench_embedding_optimizer.py [--iters 10] [--rounds 7] [--out profiles/r15_bench_embedding_optimizer.json]
     python tools/bench_embedding_optimizer.py --replicated 8 --out profiles/r17_bench_embedding_replicated.json
     python tools/bench_embedding_optimizer.py --table-dtype fp16 --out profiles/r18_bench_embedding_lowp_fp16.json
+    python tools/bench_embedding_optimizer.py --optimizer adam --out profiles/r19_bench_embedding_adam.json
 """
 import argparse
 import json
@@ -38,11 +45,12 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from generative_recommenders_amd.ops.embedding import coalesce_row_gradients, rowwise_adagrad_update_  # noqa: E402
+from generative_recommenders_amd.ops.embedding import (coalesce_row_gradients, rowwise_adagrad_update_, sparse_adam_update_,  # noqa: E402
+                                                       sparse_sgd_update_)
 from generative_recommenders_amd.ops.position import _table_grad  # noqa: E402
 
 DEV = "cuda"
-DIM, LR, EPS = 256, 0.01, 1e-8
+DIM, LR, EPS, BETAS = 256, 0.01, 1e-8, (0.9, 0.999)
 # name: (table rows, n, time the dense path too)
 SHAPES = {"1Mx256_n65536": (1_000_000, 65_536, True), "1Mx256_n1638400": (1_000_000, 1_638_400, True),
           "10Mx256_n65536": (10_000_000, 65_536, False), "10Mx256_n1638400": (10_000_000, 1_638_400, False)}
@@ -72,6 +80,59 @@ def _dense_step(weight, momentum1, idx32, dout):
     grad = _table_grad(dout, idx32, weight.shape[0])
     momentum1.add_(grad.pow(2).mean(dim=1))
     weight.addcdiv_(grad, (momentum1.sqrt() + EPS).unsqueeze(1), value=-LR)
+
+
+def run_adam_sgd(rows, n, dense, iters, rounds, optimizer):
+    """the fused sparse Adam / SGD step against _table_grad + torch.optim.Adam / SGD over the whole table"""
+    g = torch.Generator(device=DEV).manual_seed(0)
+    idx = _zipf_ids(rows, n, g)
+    idx32 = idx.to(torch.int32)
+    counts = torch.bincount(idx, minlength=1)
+    unique = int((counts > 0).sum())
+    res = {"optimizer": optimizer, "shape": {"table_rows": rows, "dim": DIM, "n": n, "unique_ids": unique,
+                                             "largest_multiplicity": int(counts.max()), "dout": "bfloat16"}}
+    del counts
+    dout = (0.01 * torch.randn(n, DIM, device=DEV, generator=g)).to(torch.bfloat16)
+    weight = torch.randn(rows, DIM, device=DEV, generator=g)
+    step = [0]
+    if optimizer == "adam":
+        exp_avg, exp_avg_sq = torch.zeros_like(weight), torch.zeros_like(weight)
+
+        def fused():
+            sparse_adam_update_(weight, exp_avg, exp_avg_sq, idx32, dout, LR, BETAS, EPS, step[0])
+            step[0] += 1
+    else:
+        fused = lambda: sparse_sgd_update_(weight, idx32, dout, LR)
+    paths = {"fused": fused}
+    if dense:
+        p2 = torch.nn.Parameter(weight.clone())
+        opt = torch.optim.Adam([p2], lr=LR, betas=BETAS, eps=EPS) if optimizer == "adam" else torch.optim.SGD([p2], lr=LR)
+
+        def dense_step():
+            p2.grad = _table_grad(dout, idx32, rows)
+            opt.step()
+
+        paths["dense"] = dense_step
+        for fn in paths.values():                                  # one step each from the same (zero) state: the results to compare
+            fn()
+        res["max_abs_diff_after_one_step"] = {"weight": float((weight - p2.detach()).abs().max())}
+    for fn in paths.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in paths}
+    for _ in range(rounds):
+        for name, fn in paths.items():
+            times[name].append(_events_ms(fn, iters))
+    alg_bytes = n * DIM * dout.element_size() + unique * ((6 * DIM * 4 + 8) if optimizer == "adam" else 2 * DIM * 4)
+    res["algorithmic_bytes"] = alg_bytes
+    res["us"] = {k: round(1e3 * statistics.median(v), 2) for k, v in times.items()}
+    res["us_rounds"] = {k: [round(1e3 * x, 2) for x in v] for k, v in times.items()}
+    res["GBps"] = {k: round(alg_bytes / (1e-3 * statistics.median(v)) / 1e9, 1) for k, v in times.items()}
+    res["share_of_8TBs"] = {k: round(alg_bytes / (1e-3 * statistics.median(v)) / 8e12, 4) for k, v in times.items()}
+    if dense:
+        res["dense_over_fused"] = round(statistics.median(times["dense"]) / statistics.median(times["fused"]), 2)
+    return res
 
 
 def run(rows, n, dense, iters, rounds):
@@ -195,12 +256,18 @@ def main():
     ap.add_argument("--replicated", type=int, default=0, metavar="W", help="time the replicated-table path with W emulated ranks")
     ap.add_argument("--table-dtype", choices=["fp32", "fp16", "bf16"], default="fp32",
                     help="fp16 / bf16: time the 16-bit table's update against the fp32 table's, alternating in one process")
+    ap.add_argument("--optimizer", choices=["adagrad", "adam", "sgd"], default="adagrad",
+                    help="adam / sgd: time the sparse Adam / SGD step against _table_grad + torch.optim.Adam / SGD (fp32 tables)")
     args = ap.parse_args()
+    if args.optimizer != "adagrad" and (args.replicated > 0 or args.table_dtype != "fp32"):
+        raise SystemExit("bench_embedding_optimizer: --optimizer adam | sgd times the fp32 one-shot step only")
     if not torch.cuda.is_available():
         raise SystemExit("bench_embedding_optimizer: needs a GPU (a timing without one says nothing)")
     res = {"device": torch.cuda.get_device_name(0), "iters": args.iters, "rounds": args.rounds, "workloads": {}}
     for name in args.shapes.split(","):
-        if args.table_dtype != "fp32":
+        if args.optimizer != "adagrad":
+            res["workloads"][name] = run_adam_sgd(*SHAPES[name], args.iters, args.rounds, args.optimizer)
+        elif args.table_dtype != "fp32":
             res["workloads"][name] = run_lowp(*SHAPES[name][:2], {"fp16": torch.float16, "bf16": torch.bfloat16}[args.table_dtype],
                                               args.iters, args.rounds)
         elif args.replicated > 0:
