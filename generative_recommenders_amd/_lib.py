@@ -185,6 +185,9 @@ SIGNATURES = {
     "hstu_input_preprocess_bwd_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, _i32, _int]),
     "hstu_input_preprocess_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _int, _f32,
                                          C.c_uint64, _int, _int, _int, _vp]),
+    "hstu_int8_row_stride": (_int, [_i32]),
+    "hstu_quantize_rows_int8": (_int, [_vp, _i64, _i64, _i32, _vp, _i64, _int, _vp]),
+    "hstu_gather_rows_int8": (_int, [_vp, _i64, _i64, _i32, _vp, _int, _i64, _vp, _i64, _int, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

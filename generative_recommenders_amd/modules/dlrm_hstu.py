@@ -12,8 +12,10 @@ switches tables to the reference's training mode, row-wise Adagrad applied in ba
 ``embedding_tables`` and the two feature arguments are duck-typed: a table needs ``name``, ``embedding_dim``,
 ``num_embeddings`` and ``feature_names``; a feature container needs ``keys()``, ``values()``, ``lengths()`` and ``[key]`` (whose result has ``values()`` and ``lengths()``).
 ``EmbeddingConfig`` and ``KeyedJaggedTensor`` below are minimal local dataclasses of those shapes; real TorchRec objects work
-unchanged.  (The reference's ``set_static_max_seq_lens`` call configures its Triton autotuner and has no counterpart here.)"""
+unchanged.  For serving, ``quantize_embeddings`` turns the trained collection into a ``QuantEmbeddingCollection`` of int8 row-wise
+quantized tables, as the reference's inference flow does (dlrm_v3/inference/model_family.py:122-143).  (The reference's ``set_static_max_seq_lens`` call configures its Triton autotuner and has no counterpart here.)"""
 
+import copy
 import logging
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, NamedTuple, Optional, Tuple
@@ -34,6 +36,7 @@ from generative_recommenders_amd.ops.embedding import (RowWiseAdagradConfig, Spa
 from generative_recommenders_amd.ops.jagged_tensors import asynchronous_complete_cumsum, concat_2D_jagged
 from generative_recommenders_amd.ops.layer_norm import LayerNorm, SwishLayerNorm
 from generative_recommenders_amd.ops.position import _table_grad
+from generative_recommenders_amd.ops.quant_embedding import gather_rows_int8, int8_row_stride, quantize_rows_int8
 
 logger: logging.Logger = logging.getLogger(__name__)
 
@@ -421,6 +424,84 @@ def apply_optimizer_in_backward(collection: Any, optimizer_name: str, learning_r
         cfg = (SparseAdamConfig(learning_rate, betas, eps, rows_dtype, replicated, process_group, average, seed)
                if optimizer_name == "Adam" else SparseSGDConfig(learning_rate, rows_dtype, replicated, process_group, average, seed))
         _set_table_optimizer(collection, table, cfg)
+
+
+# --------------------------------------------------------------------------- int8 row-wise quantized tables (inference)
+class _QuantTable(torch.nn.Module):
+    """one quantized table: the persistent buffer ``weight``, uint8 (rows, int8_row_stride(dim)) (ops/quant_embedding.py)"""
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, device: Optional[torch.device] = None) -> None:
+        super().__init__()
+        self.num_embeddings, self.embedding_dim = int(num_embeddings), int(embedding_dim)
+        self.register_buffer("weight", torch.zeros((self.num_embeddings, int8_row_stride(self.embedding_dim)), dtype=torch.uint8,
+                                                   device=device))
+
+
+class QuantEmbeddingCollection(torch.nn.Module):
+    """``EmbeddingCollection`` over int8 row-wise quantized tables, what the reference's DLRM-v3 inference flow serves
+    (dlrm_v3/inference/model_family.py:122-143: ``quantize_dynamic`` of every EmbeddingCollection, int8 weights, float
+    activations).  The same ``forward(features) -> Dict[str, JaggedTensor]`` and feature-to-table mapping; the state-dict keys
+    are ``embeddings.<table>.weight``, uint8 (rows, stride) buffers.  The forward issues ONE dequantizing gather per table over
+    the concatenated ids of all its features (``hstu_gather_rows_int8``) and splits the rows back per feature; the rows come
+    out in ``output_dtype``.  Inference only: nothing here has a gradient."""
+
+    def __init__(self, tables: List[Any], output_dtype: torch.dtype = torch.float32, device: Optional[torch.device] = None) -> None:
+        super().__init__()
+        if output_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError(f"output_dtype must be float32, float16 or bfloat16, got {output_dtype}")
+        self.embeddings = torch.nn.ModuleDict({t.name: _QuantTable(t.num_embeddings, t.embedding_dim, device) for t in tables})
+        self._output_dtype = output_dtype
+        self._feature_to_table: Dict[str, str] = {f: t.name for t in tables for f in t.feature_names}
+
+    @classmethod
+    def from_float(cls, collection: EmbeddingCollection, output_dtype: torch.dtype = torch.float32) -> "QuantEmbeddingCollection":
+        """quantize every table (FP32, FP16 or BF16) of an ``EmbeddingCollection``, on the device it lives on"""
+        names = list(collection.embeddings.keys())
+        weights = {n: collection.embeddings[n].weight.detach() for n in names}
+        tables = [EmbeddingConfig(num_embeddings=w.shape[0], embedding_dim=w.shape[1], name=n,
+                                  feature_names=[f for f, t in collection._feature_to_table.items() if t == n])
+                  for n, w in weights.items()]
+        out = cls(tables, output_dtype=output_dtype, device=torch.device("meta"))
+        for n, w in weights.items():
+            out.embeddings[n]._buffers["weight"] = quantize_rows_int8(w)
+        return out
+
+    def forward(self, features: Any) -> Dict[str, JaggedTensor]:
+        keys_of: Dict[str, List[str]] = {}
+        for key in features.keys():
+            table = self._feature_to_table.get(key)
+            if table is not None:
+                keys_of.setdefault(table, []).append(key)
+        rows_of: Dict[str, torch.Tensor] = {}
+        for table, keys in keys_of.items():
+            module = self.embeddings[table]
+            ids = [features[k].values().to(torch.int64) for k in keys]
+            rows = gather_rows_int8(module.weight, module.embedding_dim, ids[0] if len(ids) == 1 else torch.cat(ids), self._output_dtype)
+            rows_of.update(zip(keys, rows.split([i.numel() for i in ids]) if len(ids) > 1 else (rows,)))
+        return {key: JaggedTensor(rows_of[key], features[key].lengths()) for key in features.keys() if key in rows_of}
+
+
+def quantize_embeddings(module: Any, output_dtype: torch.dtype = torch.float32, inplace: bool = False) -> Any:
+    """The conversion after training, as in the reference: an ``EmbeddingCollection`` -> its ``QuantEmbeddingCollection``; a
+    ``DlrmHSTU`` -> the model with ``_embedding_collection`` replaced (a copy that shares nothing with ``module`` unless
+    ``inplace``; the float tables are not copied).  A model must be ``is_inference`` and in eval mode.  In-backward optimizer
+    state is not carried over."""
+    if isinstance(module, EmbeddingCollection):
+        return QuantEmbeddingCollection.from_float(module, output_dtype)
+    if not isinstance(module, DlrmHSTU):
+        raise TypeError(f"quantize_embeddings takes an EmbeddingCollection or a DlrmHSTU, got {type(module).__name__}")
+    if not module._is_inference:
+        raise RuntimeError("quantize_embeddings: int8 tables are for serving; the model must be built with is_inference=True")
+    if module.training:
+        raise RuntimeError("quantize_embeddings: the model is in training mode; call eval() first")
+    collection = module._embedding_collection
+    if not isinstance(collection, EmbeddingCollection):
+        raise RuntimeError(f"quantize_embeddings: the model's tables are already a {type(collection).__name__}")
+    quantized = QuantEmbeddingCollection.from_float(collection, output_dtype)
+    if not inplace:
+        module = copy.deepcopy(module, {id(collection): None})      # everything but the float tables
+    module._embedding_collection = quantized
+    return module
 
 
 def _get_supervision_labels_and_weights(

@@ -827,6 +827,37 @@ int hstu_input_preprocess_bwd(const void* d_out, const int64_t* past_ids, const 
                               float dropout_ratio, uint64_t seed, int emb_dtype, int out_dtype, int rating_index_dtype,
                               void* stream);
 
+/* ---- int8 row-wise quantized embedding tables (inference): quantize pass and dequantizing row gather -------------------
+ * The serving format of the reference's DLRM-v3 flow (dlrm_v3/inference/model_family.py:122-143: quantize_dynamic of every
+ * EmbeddingCollection to QuantEmbeddingCollection, int8 weights, float activations): fbgemm's "fused 8-bit row-wise"
+ * arithmetic, with row starts aligned for 16-byte loads.  A quantized table of rows x D is a uint8 array (rows, stride):
+ *   meta = round_up(D, 4);  stride = round_up(meta + 8, 16) = hstu_int8_row_stride(D)
+ *   bytes [0, D) the codes, [meta, meta + 4) scale (fp32, little endian), [meta + 4, meta + 8) bias (fp32), every other byte 0
+ * Per row, for x widened exactly to fp32 (all arithmetic fp32, every operation rounded on its own unless said otherwise):
+ *   mn = min(x), mx = max(x), range = mx - mn;   scale = range / 255.0f, bias = mn, inv = 255.0f / (range + 1e-8f)
+ *   code  = clamp(round_half_even((x - mn) * inv), 0, 255)             subtract, then multiply
+ *   value = code * scale + bias                                         fused multiply-add or not: both are the format
+ * A constant row has scale 0, all codes 0 and round-trips exactly.  Inputs are finite with a finite range; anything else
+ * gives unspecified values, never an access outside the buffers.  1 <= D <= 2048 (HSTU_EUNSUPPORTED above), rows and
+ * n < 2^31; row offsets are 64-bit (rows * stride may exceed 4 GiB).  No atomics, no workspace, bit-identical run to run.
+ *
+ * hstu_int8_row_stride: the stride above, or HSTU_EINVAL (dim < 1) / HSTU_EUNSUPPORTED (dim > 2048).
+ * hstu_quantize_rows_int8: src (rows, dim) in `src_dtype` (bf16, fp16, fp32), row stride in elements, unit column stride,
+ * any alignment (rows that start 16-byte aligned are read in 16-byte pieces); dst 16-byte aligned, dst_row_stride in BYTES, a
+ * multiple of 16 and >= the stride above; the first `stride` bytes of every row are written.  One pass: a group of lanes
+ * owns a row, its min / max is a wave-level exchange.  rows == 0 returns without a launch.
+ * hstu_gather_rows_int8: out[i, :] = value(table[idx[i]]) for i < n, in `out_dtype` (bf16, fp16, fp32; 16-bit outputs
+ * round the fp32 value to nearest even).  table 16-byte aligned, table_row_stride in bytes as dst_row_stride above.  idx
+ * int32 or int64 (`index_type`, HSTU_INDEX_*); idx == NULL is the identity (rows 0 .. n - 1: plain dequantization,
+ * n <= table_rows).  Ids outside [0, table_rows) are clamped (memory safety; they are the caller's error).  out_row_stride
+ * in elements (out may be a column slice of a wider tensor); every (row, 0) element 16-byte aligned.  n == 0 returns
+ * without a launch. */
+int hstu_int8_row_stride(int32_t dim);
+int hstu_quantize_rows_int8(const void* src, int64_t src_row_stride, int64_t rows, int32_t dim, void* dst, int64_t dst_row_stride,
+                            int src_dtype, void* stream);
+int hstu_gather_rows_int8(const void* table, int64_t table_row_stride, int64_t table_rows, int32_t dim, const void* idx,
+                          int index_type, int64_t n, void* out, int64_t out_row_stride, int out_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
