@@ -18,7 +18,7 @@ int launch_bwd_fold(const AttnPlan& pl, const HstuAttnBwdParams& bp, hipStream_t
   const bool quad = pl.sched == kSchedQuad;
   auto kern = quad ? hstu_attn_bwd_quad_kernel<T, 64> : (pl.a == 128 ? hstu_attn_bwd_fold_kernel<T, 128, 128> : hstu_attn_bwd_fold_kernel<T, 64, 64>);
   if (int e = reserve_lds((const void*)kern, l.smem, "hstu_attn_bwd")) return e;
-  hipLaunchKernelGGL(kern, dim3(l.grid), dim3(quad ? kQuadThreads : kBwdThreads), l.smem, st, bp, pl.nw);
+  hipLaunchKernelGGL(kern, dim3(l.grid), dim3(quad ? kQuadThreads : kBwdThreads), l.smem, st, bp, pl.nw, pl.dma_fast ? 1 : 0);
   return check_launch(quad ? "hstu_attn_bwd(quad)" : "hstu_attn_bwd(fold)");
 }
 

@@ -32,7 +32,7 @@ static int launch_bwd_fold_bias_inst(const AttnPlan& pl, const HstuAttnBwdParams
   float* partial = (float*)((char*)bp.workspace + pl.partial_off);
   int* const next_user = (int*)((char*)bp.workspace + pl.counter_off);
   if (int e = zero_workspace(partial, pl.zero_bytes, st)) return e;
-  hipLaunchKernelGGL(kern, dim3(l.grid), dim3(kBwdThreads), l.smem, st, bp, pl.nw, partial, l.ts_copies, l.hist, l.tables, next_user);
+  hipLaunchKernelGGL(kern, dim3(l.grid), dim3(kBwdThreads), l.smem, st, bp, pl.nw, pl.dma_fast ? 1 : 0, partial, l.ts_copies, l.hist, l.tables, next_user);
   if (int rc = check_launch("hstu_attn_bwd(fold, bias)")) return rc;
   return launch_bias_grad_reduce(pl, bp.workspace, 2 * bp.fwd.max_seq_len - 1, bp.dpos_w, bp.dts_w, st);
 }

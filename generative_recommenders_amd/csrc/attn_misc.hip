@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "attn_cfg.cuh"
+#include "attn_dma_addr.h"
 #include "capi_internal.h"
 namespace hstu {
 namespace {
@@ -361,6 +362,11 @@ AttnPlan plan_attn_bwd(const HstuAttnBwdParams& bp) {
     if (pl.bias) plan_partial_rows(pl, p, pl.ws_bytes, l[0].grid, false);
     if (l[0].smem > kLdsBudget)
       return refuse(pl, HSTU_EUNSUPPORTED, "hstu_attn_bwd: max_seq_len %d needs %d bytes of LDS for the bias histograms", p.max_seq_len, l[0].smem), pl;
+  }
+  // the kernels built on fold_problem_x / quad_problem: how they address their tile requests is a constant of the launch
+  if (pl.sched == kSchedFold || pl.sched == kSchedQuad || pl.sched == kSchedFoldBias) {
+    const int64_t eb = dtype_bytes(p.dtype);
+    pl.dma_fast = attn_bwd_dma_fast(p.q_row_stride * eb, p.k_row_stride * eb, p.v_row_stride * eb, bp.do_row_stride * eb, 32 * (int64_t)pl.nw);
   }
   if (pl.bias && bp.deterministic)
     refuse(pl, HSTU_EUNSUPPORTED, "hstu_attn_bwd: deterministic = 1 is not available with the relative bias (the table gradients are "

@@ -38,6 +38,7 @@ struct AttnPlan {
   int a, v;                       // padded head dims
   bool bias, head_loop, precise, contextual;
   int nw, nkb, nqb;               // key tiles per block, key blocks, query blocks (where the schedule has them)
+  bool dma_fast;                  // folded / four-wave backward: tile requests as scalar base + 32-bit lane offset (attn_dma_addr.h)
   int n_launch;
   AttnLaunch launch[2];           // solo: the length classes; long: dK / dV, dQ; general: the kernel, the dq conversion
   // backward workspace: [fp32 dq accumulator: n_slabs x slab_bytes] [partial rows x width floats] [chunk sums: chunks x width]

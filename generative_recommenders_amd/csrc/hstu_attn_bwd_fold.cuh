@@ -698,7 +698,7 @@ HSTU_DEV FoldWork fold_work(const HstuAttnParams& p, int uh, int tmax) {
 // its K/V tiles of the slots that are free during this problem's tail are requested there; `pre_lo`: in: K/V tiles >= pre_lo of THIS
 // problem were requested by the previous problem's tail; out: the same for the next one.  `kargs`: the kernel-argument segment.
 template <typename T, int DQK, int DV, typename BX = FoldNoBias>
-HSTU_DEV void fold_problem_x(const HstuAttnBwdParams& bp, kargw_t kargs, int tmax, const FoldWork& cur, const FoldWork& nxt, char* smem,
+HSTU_DEV void fold_problem_x(const HstuAttnBwdParams& bp, kargw_t kargs, bool dma_fast, const FoldWork& cur, const FoldWork& nxt, char* smem,
                              int tid, int lane, int wave, int& pre_lo, BX& bx) {
   using C = BwdCfg<T, DQK, DV>;
   using F = FoldCfg<T, DQK, DV>;
@@ -731,11 +731,10 @@ HSTU_DEV void fold_problem_x(const HstuAttnBwdParams& bp, kargw_t kargs, int tma
                 do_rs = bp.do_row_stride * C::EB;
 
   // LDS-DMA source addresses as scalar base + 32-bit lane offset (3 instead of ~20 VALU per chunk; fold_tile_dma): strides < 16 MiB
-  // and a user's rows within 4 GiB of its first (the same test covers the next problem's K/V rows requested from this one's tail)
-  const int len_max = 32 * tmax;
-  const bool dma_fast = q_rs < (1 << 24) && k_rs < (1 << 24) && v_rs < (1 << 24) && do_rs < (1 << 24) &&
-                        (int64_t)len_max * q_rs < (1LL << 32) && (int64_t)len_max * k_rs < (1LL << 32) &&
-                        (int64_t)len_max * v_rs < (1LL << 32) && (int64_t)len_max * do_rs < (1LL << 32);
+  // and a user's rows within 4 GiB of its first (the same test covers the next problem's K/V rows requested from this one's tail).
+  // `dma_fast` is a constant of the launch -- four strides and 32 tmax -- and comes from the host (attn_dma_addr.h) as a kernel
+  // argument.  Evaluated here, per problem, its last 64-bit compare kept a constant in a spilled register pair: a scratch reload
+  // and an s_waitcnt vmcnt(0) -- a wait for the previous problem's copy-out stores -- in front of the first request below.
   auto stage_dma = [&](int qa, int qb, bool b_on) {
     fold_tile_dma<T, DQK>(stageA, qbase, q_rs, 32 * qa, len, wave, lane, dma_fast);
     fold_tile_dma<T, DV>(stageA + C::KT, dobase, do_rs, 32 * qa, len, wave, lane, dma_fast);
@@ -922,7 +921,7 @@ HSTU_DEV void fold_problem_x(const HstuAttnBwdParams& bp, kargw_t kargs, int tma
 // problems of a CU: the dispatch gap, the kernel-argument loads and the wave start-up are paid once) and requests the next problem's
 // K/V tiles of the slots its own tail does not use.
 template <typename T, int DQK, int DV>
-__global__ __launch_bounds__(kBwdThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void hstu_attn_bwd_fold_kernel(const HstuAttnBwdParams bp_arg, int tmax) {
+__global__ __launch_bounds__(kBwdThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void hstu_attn_bwd_fold_kernel(const HstuAttnBwdParams bp_arg, int tmax, int dma_fast) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -943,7 +942,7 @@ __global__ __launch_bounds__(kBwdThreads) __attribute__((amdgpu_waves_per_eu(2, 
     FoldWork nxt;
     nxt.len = 0; nxt.off0 = 0; nxt.b = 0; nxt.hd = 0;
     if (uh + (int)gridDim.x < total) nxt = fold_work(bp.fwd, uh + (int)gridDim.x, tmax);
-    fold_problem_x<T, DQK, DV, FoldNoBias>(bp, kl, tmax, cur, nxt, smem, tid, lane, wave, pre_lo, nb);
+    fold_problem_x<T, DQK, DV, FoldNoBias>(bp, kl, dma_fast != 0, cur, nxt, smem, tid, lane, wave, pre_lo, nb);
     cur = nxt;
     __syncthreads();                   // the tail's LDS reads are done before the next prologue's DMA lands
   }
@@ -956,7 +955,7 @@ __global__ __launch_bounds__(kBwdThreads) __attribute__((amdgpu_waves_per_eu(2, 
 // LDS behind the folded kernel's own region: [pos histogram 2N][time histogram (nb+1) x ts_copies][tables][bucket bytes].
 template <typename T, int D>
 __global__ __launch_bounds__(kBwdThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void hstu_attn_bwd_fold_bias_kernel(
-    const HstuAttnBwdParams bp_arg, int tmax, float* bias_partial, int ts_copies, int hist_bytes, int table_bytes, int* next_user) {
+    const HstuAttnBwdParams bp_arg, int tmax, int dma_fast, float* bias_partial, int ts_copies, int hist_bytes, int table_bytes, int* next_user) {
   using F = FoldCfg<T, D, D>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
@@ -1017,7 +1016,7 @@ __global__ __launch_bounds__(kBwdThreads) __attribute__((amdgpu_waves_per_eu(2, 
       if (hd + 1 < heads) { nxt = cur; nxt.hd = hd + 1; }            // the same user's next head: no load
       else if (uh_n >= 0) nxt = fold_work(bp.fwd, uh_n, tmax);
       bx.cached = hd > 0;
-      fold_problem_x<T, D, D, FoldBias>(bp, kl, tmax, cur, nxt, smem, tid, lane, wave, pre_lo, bx);
+      fold_problem_x<T, D, D, FoldBias>(bp, kl, dma_fast != 0, cur, nxt, smem, tid, lane, wave, pre_lo, bx);
       cur = nxt;
       __syncthreads();
     }

@@ -118,7 +118,7 @@ HSTU_DEV void quad_dq_phase(const HstuAttnBwdParams& bp, const MaskCtx& mc, cons
 }
 
 template <typename T, int D>
-HSTU_DEV void quad_problem(const HstuAttnBwdParams& bp, int tmax, int uh, char* smem, int tid, int lane, int wave) {
+HSTU_DEV void quad_problem(const HstuAttnBwdParams& bp, int tmax, bool dma_fast, int uh, char* smem, int tid, int lane, int wave) {
   using C = BwdCfg<T, D, D>;
   using Q = QuadCfg<T, D>;
   static_assert(C::EB == 2, "16-bit I/O");
@@ -143,10 +143,7 @@ HSTU_DEV void quad_problem(const HstuAttnBwdParams& bp, int tmax, int uh, char* 
   const int64_t q_rs = p.q_row_stride * C::EB, k_rs = p.k_row_stride * C::EB, v_rs = p.v_row_stride * C::EB,
                 do_rs = bp.do_row_stride * C::EB;
 
-  const int len_max = 32 * tmax;
-  const bool dma_fast = q_rs < (1 << 24) && k_rs < (1 << 24) && v_rs < (1 << 24) && do_rs < (1 << 24) &&
-                        (int64_t)len_max * q_rs < (1LL << 32) && (int64_t)len_max * k_rs < (1LL << 32) &&
-                        (int64_t)len_max * v_rs < (1LL << 32) && (int64_t)len_max * do_rs < (1LL << 32);
+  // (`dma_fast`: scalar base + 32-bit lane offsets, decided once per launch on the host: attn_dma_addr.h)
   auto stage_dma = [&](int qt) {
     quad_tile_dma<T, D>(stage, qbase, q_rs, 32 * qt, len, wave, lane, dma_fast);
     quad_tile_dma<T, D>(stage + C::KT, dobase, do_rs, 32 * qt, len, wave, lane, dma_fast);
@@ -238,12 +235,12 @@ HSTU_DEV void quad_problem(const HstuAttnBwdParams& bp, int tmax, int uh, char* 
 }
 
 template <typename T, int D>
-__global__ __launch_bounds__(kQuadThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void hstu_attn_bwd_quad_kernel(const HstuAttnBwdParams bp, int tmax) {
+__global__ __launch_bounds__(kQuadThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void hstu_attn_bwd_quad_kernel(const HstuAttnBwdParams bp, int tmax, int dma_fast) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  quad_problem<T, D>(bp, tmax, blockIdx.x, smem, tid, lane, wave);   // one workgroup per (user, head) problem
+  quad_problem<T, D>(bp, tmax, dma_fast != 0, blockIdx.x, smem, tid, lane, wave);   // one workgroup per (user, head) problem
 }
 
 }  // namespace hstu

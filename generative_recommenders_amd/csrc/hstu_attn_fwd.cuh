@@ -27,8 +27,9 @@ namespace hstu {
 #define HSTU_FWD_MIN_WAVES 2
 #endif
 // (round 6: the measured-and-lost switches of this kernel -- K tiles three ahead behind a second barrier, first tiles requested in front of
-// the Q rows, wave priority by phase, the conflict-free park of the output tile, the builtin form of the DMA instruction -- left the
-// source; the version that carried them: docs/experiments/r06_hstu_attn_fwd_with_switches.cuh.txt, results docs/EXPERIMENTS.md A.3, R5.7)
+// the Q rows (but see the note at the Q rows below: the binary did not change its order), wave priority by phase, the conflict-free
+// park of the output tile, the builtin form of the DMA instruction -- left the source; the version that carried them:
+// docs/experiments/r06_hstu_attn_fwd_with_switches.cuh.txt, results docs/EXPERIMENTS.md A.3, R5.7)
 // Cooperative global -> register load of one [32][D] tile and the matching register -> LDS
 // write.  The loads are UNCONDITIONAL on clamped (always valid) addresses so that nothing
 // consumes the loaded registers until tile_lds_write: the global loads stay in flight across
@@ -179,6 +180,66 @@ HSTU_DEV typename Elem<T>::Frag finish_row_frag(const RawFrag<T>& r, bool ok, bo
   return f;
 }
 
+// The Q rows of a 16-bit instantiation with a counted ring: requested and waited for BY HAND, so that the wait can say what is
+// meant -- "my KG row loads have landed; the tile requests issued behind them may still be in flight".  With ordinary loads
+// hipcc sinks the fragments' selects below the first tiles' DMA instructions (inline asm: invisible to its waitcnt pass) and
+// guards them with vmcnt(KG-1) .. vmcnt(0), counted for its own loads only: with the DMA requests behind them the last of those
+// waits drains the ring, and the first S chain starts when tile 1 has landed as well as tile 0 and Q.  Here the loads go
+// through asm too (the compiler sees registers that are simply defined), and one s_waitcnt vmcnt(N), N = the DMA instructions
+// the wave has issued since, hands the registers over: memory operations complete in order, so everything older than the N
+// newest -- the Q rows and whatever was outstanding before them -- is done.  Nothing may touch `raw` between the two calls.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+template <int KG, int I = 0>
+HSTU_DEV void q_rows_issue(u32x4 (&raw)[KG], const char* ptr) {
+  if constexpr (I < KG) {
+    asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=&v"(raw[I]) : "v"(ptr), "n"(16 * I) : "memory");
+    q_rows_issue<KG, I + 1>(raw, ptr);
+  }
+}
+// `two` (wave-uniform): the wave has requested two tiles since its rows (N2 instructions), else one (N1).  One statement with
+// its own branch: two statements in an if / else would meet at a join, and the copies hipcc placed there to bring their tied
+// operands together read the registers BEFORE the wait (seen in the disassembly of the first version of this).
+#define HSTU_QWAIT_ASM                                                                                                     \
+  "s_cmp_eq_u32 %[two], 0\n\ts_cbranch_scc1 .Lhstu_qw1_%=\n\ts_waitcnt vmcnt(%[n2])\n\ts_branch .Lhstu_qw2_%=\n"           \
+  ".Lhstu_qw1_%=:\n\ts_waitcnt vmcnt(%[n1])\n.Lhstu_qw2_%=:"
+template <int N1, int N2>
+HSTU_DEV void q_rows_wait(u32x4 (&r)[8], int two) {
+  asm volatile(HSTU_QWAIT_ASM
+               : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7])
+               : [two] "s"(two), [n1] "n"(N1), [n2] "n"(N2)
+               : "memory", "scc");
+}
+template <int N1, int N2>
+HSTU_DEV void q_rows_wait(u32x4 (&r)[4], int two) {
+  asm volatile(HSTU_QWAIT_ASM : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]) : [two] "s"(two), [n1] "n"(N1), [n2] "n"(N2) : "memory", "scc");
+}
+#undef HSTU_QWAIT_ASM
+// A head dim below the instantiated one: fragment kg of a lane starts at element e_first + 8 kg of its row, or at element 0 when
+// that lies past the real head dim (never read past the row; the caller zeroes such a fragment).  Loads and their wait in ONE
+// statement: the registers are complete when the compiler first sees them.
+#define HSTU_QROW_PTR(kg) (row_ptr + ((e_first + 8 * (kg)) < real_d ? (e_first + 8 * (kg)) * 2 : 0))
+HSTU_DEV void q_rows_load_clamped(u32x4 (&r)[8], const char* row_ptr, int e_first, int real_d) {
+  asm volatile(
+      "global_load_dwordx4 %0, %8, off\n\tglobal_load_dwordx4 %1, %9, off\n\tglobal_load_dwordx4 %2, %10, off\n\t"
+      "global_load_dwordx4 %3, %11, off\n\tglobal_load_dwordx4 %4, %12, off\n\tglobal_load_dwordx4 %5, %13, off\n\t"
+      "global_load_dwordx4 %6, %14, off\n\tglobal_load_dwordx4 %7, %15, off\n\ts_waitcnt vmcnt(0)"
+      : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(r[4]), "=&v"(r[5]), "=&v"(r[6]), "=&v"(r[7])
+      : "v"(HSTU_QROW_PTR(0)), "v"(HSTU_QROW_PTR(1)), "v"(HSTU_QROW_PTR(2)), "v"(HSTU_QROW_PTR(3)), "v"(HSTU_QROW_PTR(4)),
+        "v"(HSTU_QROW_PTR(5)), "v"(HSTU_QROW_PTR(6)), "v"(HSTU_QROW_PTR(7))
+      : "memory");
+}
+HSTU_DEV void q_rows_load_clamped(u32x4 (&r)[4], const char* row_ptr, int e_first, int real_d) {
+  asm volatile(
+      "global_load_dwordx4 %0, %4, off\n\tglobal_load_dwordx4 %1, %5, off\n\tglobal_load_dwordx4 %2, %6, off\n\t"
+      "global_load_dwordx4 %3, %7, off\n\ts_waitcnt vmcnt(0)"
+      : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3])
+      : "v"(HSTU_QROW_PTR(0)), "v"(HSTU_QROW_PTR(1)), "v"(HSTU_QROW_PTR(2)), "v"(HSTU_QROW_PTR(3))
+      : "memory");
+}
+#undef HSTU_QROW_PTR
+#pragma clang diagnostic pop
+
 // Store a transposed accumulator block: this lane holds, for output row `row_ptr`,
 // the 4 consecutive columns d0..d0+3 in acc[4*rq .. 4*rq+3].
 template <typename T>
@@ -308,9 +369,16 @@ __global__ __launch_bounds__(kFwdThreads, PRECISE ? 2 : HSTU_FWD_MIN_WAVES) void
     }                                                                                                                        \
   }
   // ---- Q fragment of this wave (B operand of S^T = K Q^T): lane (q = n32, hf) holds elements hf*DQK/2 + 8*kg .. +8 of its
-  // row: one contiguous half row per lane.  (Requesting the first K/V tiles BEFORE the Q rows measured 1.6 % slower, twice.)
-  HSTU_FWD_LOAD_Q()
-  HSTU_MARK(2);
+  // row: one contiguous half row per lane.  The rows are requested FIRST and the first K/V tiles behind them.  (The note that
+  // stood here, "requesting the first K/V tiles before the Q rows measured 1.6 % slower, twice", compared two sources that
+  // compiled to the same request order -- hipcc moved the fragments' selects below the DMA instructions either way -- and what
+  // it measured was where the compiler's vmcnt(0) for the last Q row fell: q_rows_wait, docs/EXPERIMENTS.md R21.)
+  // 16-bit I/O, head dim 128, a counted ring: loads and wait by hand, see q_rows_issue.  (!COUNTED instantiations -- waves with
+  // different chunk counts per tile, a two-deep ring -- and fp32 rows keep the compiler's loads and waits.  So does head dim 64:
+  // there the hand-written wait measured 2.5 % SLOWER, 0.720 -> 0.738 ms at 8192 users -- four row loads are back before the
+  // second tile's requests are out, and the asm loads cannot be hoisted to the top of the kernel as the compiler's are:
+  // docs/EXPERIMENTS.md R21.  The KG == 4 overloads stay for that experiment.)
+  constexpr bool kQAsm = C::EB == 2 && C::COUNTED && C::KG == 8;
   const char* kbase = (const char*)p.k + (off0 * p.k_row_stride + (int64_t)hd * p.k_head_stride) * C::EB;
   const char* vbase = (const char*)p.v + (off0 * p.v_row_stride + (int64_t)hd * p.v_head_stride) * C::EB;
   const int64_t k_rs = p.k_row_stride * C::EB, v_rs = p.v_row_stride * C::EB;
@@ -362,7 +430,37 @@ __global__ __launch_bounds__(kFwdThreads, PRECISE ? 2 : HSTU_FWD_MIN_WAVES) void
   };
   // (K tiles three ahead -- K(t+3) requested in the middle of step t behind a second barrier, +12 % bytes in flight in the same LDS --
   // measured bit-identical and 0.7 % / 3 % SLOWER: the second barrier costs more than the lead buys, profiles/r03_ab_fwd_k_early.txt)
-  for (int t = 0; t < C::NS - 1 && t < ntiles; ++t) issue_tile(t, t);
+  auto issue_first_tiles = [&]() {
+    for (int t = 0; t < C::NS - 1 && t < ntiles; ++t) issue_tile(t, t);
+  };
+  if constexpr (kQAsm) {
+    const int ld_row = min(my_row, nq_rows - 1);   // clamped: always a valid row of this user
+    const char* qrow = (const char*)p.q + ((q_base + ld_row) * p.q_row_stride + (int64_t)hd * p.q_head_stride) * C::EB;
+    u32x4 qraw[C::KG];
+    // (each branch requests the tiles itself: no control-flow join while the row registers are in flight -- a copy the compiler
+    // placed at one would read them before they have landed)
+    if (p.dqk == DQK) {        // workgroup-uniform
+      q_rows_issue<C::KG>(qraw, qrow + hf * (DQK / 2) * C::EB);
+      HSTU_MARK(2);
+      issue_first_tiles();
+      // The wave has issued PER_TILE DMA instructions per tile since its Q rows, on the planned and on the general address path
+      // alike (COUNTED: every wave takes NCH / 4 chunks of a tile); ntiles >= 1
+      static_assert(C::NS == 3, "16-bit counted rings are three deep: one or two tiles requested up front");
+      q_rows_wait<C::PER_TILE, 2 * C::PER_TILE>(qraw, __builtin_amdgcn_readfirstlane(ntiles >= 2 ? 1 : 0));
+    } else {                   // a head dim below the instantiated one: per-fragment clamped addresses, waited for on the spot
+      q_rows_load_clamped(qraw, qrow, hf * (DQK / 2), p.dqk);
+      HSTU_MARK(2);
+      issue_first_tiles();
+    }
+    const u32x4 z = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int kg = 0; kg < C::KG; ++kg)
+      qf[kg].v = __builtin_bit_cast(typename E::vec8, (row_ok && hf * (DQK / 2) + kg * 8 < p.dqk) ? qraw[kg] : z);
+  } else {
+    HSTU_FWD_LOAD_Q()
+    HSTU_MARK(2);
+    issue_first_tiles();
+  }
 #undef HSTU_FWD_LOAD_Q
   HSTU_MARK(3);
 

@@ -463,8 +463,16 @@ HSTU_DEV int user_of_slot_s(const HstuAttnParams& p, int slot) {      // (wave-u
   return p.user_order ? (int)sload_index(p.user_order, slot, 0) : slot;
 }
 
-// 1/N, or the caller's device-side replacement for it (HstuAttnParams::attn_scale: the reference's attn_scale[0])
-HSTU_DEV float attn_scale_of(const HstuAttnParams& p) { return p.attn_scale ? *p.attn_scale : p.scale; }
+// 1/N, or the caller's device-side replacement for it (HstuAttnParams::attn_scale: the reference's attn_scale[0]).  Read on
+// the device in every launch (the caller may rewrite it between two), through the CONSTANT address space like sload_index:
+// the pointer is a kernel argument, so hipcc emits s_load_dword, which lgkmcnt counts.  The plain dereference was a
+// conditional flat_load_dword whose s_waitcnt vmcnt(0) sat at the join -- executed with or without the pointer -- and in the
+// persistent backward kernels that is a wait for every tile request of the problem's prologue in front of work that needs none
+// of them.  No kernel writes the value: the scalar cache's incoherence with vector stores does not matter.
+HSTU_DEV float attn_scale_of(const HstuAttnParams& p) {
+  typedef const __attribute__((address_space(4))) float* cf32;
+  return p.attn_scale ? *(cf32)(uintptr_t)p.attn_scale : p.scale;
+}
 
 // silu(s) = s * sigmoid(s), fp32, hardware exp2 / rcp (1 ulp each)
 HSTU_DEV float fast_sigmoid(float s) {
