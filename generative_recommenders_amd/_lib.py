@@ -109,6 +109,10 @@ SIGNATURES = {
     "hstu_layer_norm_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _int, _vp]),
     "hstu_ln_linear_fwd_supported": (_int, [_i64, _i32, _i32, _int]),
     "hstu_ln_linear_fwd": (_int, [_vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _int, _vp]),
+    "hstu_ln_linear_fp8_supported": (_int, [_i64, _i32, _i32, _int]),
+    "hstu_quantize_rows_fp8": (_int, [_vp, _i64, _i64, _i32, _int, _vp, _vp, _vp]),
+    "hstu_ln_linear_fp8_fwd": (_int, [_vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _int, _vp]),
+    "hstu_linear_fp8_rowwise": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _int, _vp]),
     "hstu_linear_k512_supported": (_int, [_i64, _i32, _i32, _int]),
     "hstu_linear_k512": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _int, _vp]),
     "hstu_addmm_residual_supported": (_int, []),

@@ -59,6 +59,10 @@ class STULayerConfig:
     recompute_y: bool = True
     sort_by_length: bool = True
     contextual_seq_len: int = 0
+    # the UVQK projection's forward (and backward's recompute of it) on row-wise e4m3 operands -- the reference's switch of
+    # this name (ops/cpp/cuda_hstu_preprocess_and_attention.py).  Needs embedding_dim == 512 and CUDA bf16 / fp16 activations:
+    # anything else raises a ValueError, there is no 16-bit fallback.  Backward's own GEMMs stay 16-bit.
+    fp8_in_addmm_fwd: bool = False
 
 
 def _split_cache(max_seq_len, seq_offsets, kv, kv_caching_offsets, delta_offsets):
@@ -91,6 +95,7 @@ class STULayer(STU):
         self.fuse_layer = os.environ.get("HSTU_FUSE_LAYER", "1") != "0"
         self._sort_by_length = config.sort_by_length
         self._contextual_seq_len = config.contextual_seq_len
+        self._fp8_in_addmm_fwd = bool(config.fp8_in_addmm_fwd)
 
         proj = (self._hidden_dim * 2 + self._attention_dim * 2) * self._num_heads
         self._uvqk_weight = torch.nn.Parameter(torch.empty((self._embedding_dim, proj)))
@@ -187,7 +192,8 @@ class STULayer(STU):
                     group_norm=self._use_group_norm,
                     recompute_uvqk_in_backward=self._recompute_uvqk,
                     recompute_normed_x_in_backward=self._recompute_normed_x,
-                    recompute_y_in_backward=self._recompute_y, sort_by_length=self._sort_by_length)
+                    recompute_y_in_backward=self._recompute_y, sort_by_length=self._sort_by_length,
+                    fp8_in_addmm_fwd=self._fp8_in_addmm_fwd)
             self.update_kv_cache(max_seq_len=max_seq_len, seq_offsets=x_offsets, k=None, v=None,
                                  max_kv_caching_len=max_kv_caching_len, kv_caching_lengths=kv_caching_lengths)
             return out
@@ -214,6 +220,7 @@ class STULayer(STU):
                 sort_by_length=self._sort_by_length,
                 prefill=kv_caching_lengths is not None,
                 kernel=self.hammer_kernel(),
+                fp8_in_addmm_fwd=self._fp8_in_addmm_fwd,
             )
         self.update_kv_cache(max_seq_len=max_seq_len, seq_offsets=x_offsets, k=k, v=v,
                              max_kv_caching_len=max_kv_caching_len, kv_caching_lengths=kv_caching_lengths)
@@ -252,6 +259,7 @@ class STULayer(STU):
                 uvqk_weight=self._uvqk_weight.to(delta_x.dtype),
                 uvqk_bias=self._uvqk_beta.to(delta_x.dtype),
                 kernel=self.hammer_kernel(),
+                fp8_in_addmm_fwd=self._fp8_in_addmm_fwd,
             )
         k, v, max_seq_len, seq_offsets = self.construct_full_kv(delta_k=delta_k.flatten(1, 2),
                                                                 delta_v=delta_v.flatten(1, 2))

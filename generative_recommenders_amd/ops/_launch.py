@@ -701,6 +701,69 @@ def linear_k512(x, w_nk, bias=None):
     return y
 
 
+def quantize_rows_fp8(src):
+    """(codes, scale) of the rows of a 2-D bf16 / fp16 / fp32 tensor (hstu_quantize_rows_fp8): codes e4m3 (rows, k) contiguous,
+    scale fp32 per row = amax / 448 (1 for a zero row), codes = e4m3(clamp(src / scale, -448, 448))"""
+    L.require_gpu_tensor(src, "src")
+    torch._assert(src.dim() == 2 and src.stride(1) == 1, "src must be 2-D with a contiguous last dimension")
+    rows, k = src.shape
+    q = torch.empty((rows, k), dtype=torch.float8_e4m3fn, device=src.device)
+    scale = _f32(rows, src.device)
+    with torch.cuda.device(src.device):
+        L.check(L.lib().hstu_quantize_rows_fp8(src.data_ptr(), src.stride(0), rows, k, L.torch_dtype_code(src.dtype), q.data_ptr(),
+                                               scale.data_ptr(), L.current_stream_ptr(src.device)))
+    return q, scale
+
+
+def ln_linear_fp8_supported(x, n):
+    """whether the row-wise e4m3 LayerNorm + projection kernel takes (rows, k) activations and n output columns"""
+    return bool(x.is_cuda and x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16) and
+                L.lib().hstu_ln_linear_fp8_supported(x.shape[0], x.shape[1], n, L.torch_dtype_code(x.dtype)))
+
+
+def ln_linear_fp8_fwd(x, ln_weight, ln_bias, eps, wq, w_scale, bias, want_q=False):
+    """y = (q(LayerNorm(x)) @ wq.T) * x_scale[:, None] * w_scale + bias in one kernel (csrc/hstu_ln_linear_fp8.cuh): returns
+    (y, xq or None, x_scale or None, mean, rstd).  ``(wq, w_scale)``: quantize_rows_fp8 of the (n, k) K-contiguous weight."""
+    L.require_gpu_tensor(x, "x")
+    x = x.contiguous()
+    rows, k = x.shape
+    n = wq.shape[0]
+    torch._assert(wq.shape[1] == k and wq.is_contiguous() and wq.dtype == torch.float8_e4m3fn, "wq must be a contiguous (n, k) e4m3 tensor")
+    torch._assert(w_scale.shape == (n,) and w_scale.dtype == torch.float32 and w_scale.is_contiguous(), "w_scale must be n fp32 values")
+    y = torch.empty((rows, n), dtype=x.dtype, device=x.device)
+    xq = torch.empty((rows, k), dtype=torch.float8_e4m3fn, device=x.device) if want_q else None
+    x_scale = _f32(rows, x.device) if want_q else None
+    mean, rstd = _f32(rows, x.device), _f32(rows, x.device)
+    w, b = ln_weight.to(x.dtype).contiguous(), ln_bias.to(x.dtype).contiguous()
+    pb = None if bias is None else bias.to(x.dtype).contiguous()
+    with torch.cuda.device(x.device):
+        L.check(L.lib().hstu_ln_linear_fp8_fwd(x.data_ptr(), k, w.data_ptr(), b.data_ptr(), float(eps), wq.data_ptr(), w_scale.data_ptr(),
+                                               None if pb is None else pb.data_ptr(), y.data_ptr(), n,
+                                               None if xq is None else xq.data_ptr(), None if x_scale is None else x_scale.data_ptr(),
+                                               mean.data_ptr(), rstd.data_ptr(), rows, k, n, L.torch_dtype_code(x.dtype),
+                                               L.current_stream_ptr(x.device)))
+    return y, xq, x_scale, mean, rstd
+
+
+def linear_fp8_rowwise(xq, x_scale, wq, w_scale, bias=None, out_dtype=torch.bfloat16):
+    """y = (xq @ wq.T) * x_scale[:, None] * w_scale (+ bias) on e4m3 codes with row-wise scales (the fp8 kernel without its
+    LayerNorm): xq (rows, 512), wq (n, 512) contiguous e4m3, scales fp32"""
+    L.require_gpu_tensor(xq, "xq")
+    rows, k = xq.shape
+    n = wq.shape[0]
+    torch._assert(xq.is_contiguous() and wq.is_contiguous() and xq.dtype == torch.float8_e4m3fn and wq.dtype == torch.float8_e4m3fn and
+                  wq.shape[1] == k, "xq and wq must be contiguous e4m3 tensors with the same k")
+    torch._assert(x_scale.shape == (rows,) and w_scale.shape == (n,) and x_scale.dtype == torch.float32 and w_scale.dtype == torch.float32 and
+                  x_scale.is_contiguous() and w_scale.is_contiguous(), "x_scale / w_scale must be fp32, one per row")
+    y = torch.empty((rows, n), dtype=out_dtype, device=xq.device)
+    pb = None if bias is None else bias.to(out_dtype).contiguous()
+    with torch.cuda.device(xq.device):
+        L.check(L.lib().hstu_linear_fp8_rowwise(xq.data_ptr(), x_scale.data_ptr(), wq.data_ptr(), w_scale.data_ptr(),
+                                                None if pb is None else pb.data_ptr(), y.data_ptr(), n, rows, k, n,
+                                                L.torch_dtype_code(out_dtype), L.current_stream_ptr(xq.device)))
+    return y
+
+
 _ADDMM_LT = os.environ.get("HSTU_ADDMM_LT", "1") != "0"      # 0: torch.addmm (copy + in-place GEMM), the comparator
 _ADDMM_WS: dict = {}          # device -> hipBLASLt workspace (32 MiB, as PyTorch's own), allocated once
 

@@ -33,10 +33,15 @@ def hstu_compute_uqvk(
     uvqk_weight: torch.Tensor,
     uvqk_bias: torch.Tensor,
     kernel: HammerKernel = HammerKernel.HIP,
+    fp8_in_addmm_fwd: bool = False,
 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    """LN_affine(x) @ W + b, split as [u, v, q, k], SiLU on u only."""
+    """LN_affine(x) @ W + b, split as [u, v, q, k], SiLU on u only.  ``fp8_in_addmm_fwd`` (the reference's name): the
+    projection's forward on row-wise e4m3 operands (csrc/hstu_ln_linear_fp8.cuh); backward stays 16-bit."""
     del kernel
-    if _LN_LINEAR and _UVQK_LINEAR and x.is_cuda and x.dim() == 2 and _launch.ln_linear_supported(x, uvqk_weight.shape[1]):
+    if fp8_in_addmm_fwd:
+        _fp8_require(x, uvqk_weight.shape[1])
+        uvqk = _LnUvqkFunction.apply(x, norm_weight, norm_bias, uvqk_weight, uvqk_bias, norm_eps, torch.is_grad_enabled(), True)
+    elif _LN_LINEAR and _UVQK_LINEAR and x.is_cuda and x.dim() == 2 and _launch.ln_linear_supported(x, uvqk_weight.shape[1]):
         # the fused LayerNorm + projection kernel (one autograd node), as the STU layer's nodes use it: the K / V rows a delta
         # call appends to a cache are then bit-identical to the ones the prefill wrote (a row's result does not depend on its
         # neighbours in the batch)
@@ -67,12 +72,14 @@ class _LnUvqkFunction(torch.autograd.Function):
     gradients (hipBLASLt) + the layer-norm backward kernel, normed_x recomputed by the row kernel (as the STU layer's nodes do)."""
 
     @staticmethod
-    def forward(ctx, x, norm_weight, norm_bias, uvqk_weight, uvqk_bias, eps, grad_on=True):
+    def forward(ctx, x, norm_weight, norm_bias, uvqk_weight, uvqk_bias, eps, grad_on=True, fp8=False):
         # (``grad_on``: the caller's grad mode -- inside forward it is always off, and needs_input_grad ignores it)
         ctx.param_dtypes = (norm_weight.dtype, norm_bias.dtype, uvqk_weight.dtype, uvqk_bias.dtype)
-        (nw, nb, w, beta), kmajor = _prepare_params((norm_weight, norm_bias, uvqk_weight, uvqk_bias), x.dtype, 2,
-                                                    grad_on and any(ctx.needs_input_grad))
-        uvqk, _, mean, rstd = _ln_uvqk(x, nw, nb, eps, w, kmajor, beta, want_normed=False)
+        tracked = grad_on and any(ctx.needs_input_grad)
+        (nw, nb, w, beta), kmajor = _prepare_params((norm_weight, norm_bias, uvqk_weight, uvqk_bias), x.dtype, 2, tracked)
+        # (fp8: backward of this node does not form uvqk again, so the codes are not saved)
+        uvqk, _, mean, rstd = _ln_uvqk(x, nw, nb, eps, w, kmajor, beta, want_normed=False,
+                                       fp8=_fp8_weight(x, w, kmajor, tracked) if fp8 else None)
         ctx.save_for_backward(x, nw, nb, mean, rstd, w)
         ctx.kmajor, ctx.eps = kmajor, eps
         return uvqk
@@ -87,7 +94,7 @@ class _LnUvqkFunction(torch.autograd.Function):
         d_normed = _uvqk_dgrad(duvqk, w, ctx.kmajor)
         dW = weight_grad_mm(normed_x, duvqk, out_dtype=dt[2])
         dx, dnw, dnb = _launch.layer_norm_bwd(d_normed, x, nw, mean, rstd)
-        return dx, dnw.to(dt[0]), dnb.to(dt[1]), dW, dbeta.to(dt[3]), None, None
+        return dx, dnw.to(dt[0]), dnb.to(dt[1]), dW, dbeta.to(dt[3]), None, None, None
 
 
 class _SiluFunction(torch.autograd.Function):
@@ -129,6 +136,36 @@ def invalidate_parameter_caches() -> None:
     the counter: call this afterwards.  Calls that track gradients (training) never read the caches."""
     _KMAJOR_CACHE.clear()
     _PARAM_CACHE.clear()
+    _FP8_WEIGHT_CACHE.clear()
+
+
+_FP8_WEIGHT_CACHE: dict = {}   # id(cached K-major 16-bit copy) -> (weak reference, (wq, w_scale)): lives and dies with that copy
+
+
+def _fp8_require(x: torch.Tensor, n: int) -> None:
+    """fp8_in_addmm_fwd has no 16-bit fallback: a shape its kernel does not take is the caller's error"""
+    if not (x.is_cuda and x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16) and _launch.ln_linear_fp8_supported(x, n)):
+        raise ValueError(
+            f"fp8_in_addmm_fwd needs CUDA bf16 / fp16 activations with an embedding dim of 512 and at most 4096 projection columns "
+            f"in multiples of 32 (got {'cuda' if x.is_cuda else 'cpu'} {x.dtype}, embedding dim {x.shape[-1]}, {n} columns)")
+    if not (_LN_LINEAR and _UVQK_LINEAR):
+        raise ValueError("fp8_in_addmm_fwd needs the fused LayerNorm + projection path (HSTU_LN_LINEAR / HSTU_UVQK_LINEAR are off)")
+
+
+def _fp8_weight(x: torch.Tensor, w: torch.Tensor, kmajor: bool, tracked: bool):
+    """(wq, w_scale): the K-major 16-bit weight copy quantized row by row -- one launch per forward for a call that tracks
+    gradients; otherwise kept beside the copy the parameter cache holds, for as long as that copy lives"""
+    _fp8_require(x, w.shape[0] if kmajor else w.shape[1])
+    torch._assert(kmajor, "fp8_in_addmm_fwd multiplies by the K-major weight copy")
+    if tracked or not _PARAM_CACHE_ON:
+        return _launch.quantize_rows_fp8(w)
+    wid = id(w)
+    hit = _FP8_WEIGHT_CACHE.get(wid)
+    if hit is not None and hit[0]() is w:
+        return hit[1]
+    pair = _launch.quantize_rows_fp8(w)
+    _FP8_WEIGHT_CACHE[wid] = (weakref.ref(w, lambda _r, wid=wid: _FP8_WEIGHT_CACHE.pop(wid, None)), pair)
+    return pair
 
 
 def _kmajor(weight: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
@@ -221,18 +258,27 @@ def _uvqk_gemm(normed_x: torch.Tensor, w: torch.Tensor, kmajor: bool, bias: torc
 _LN_LINEAR = os.environ.get("HSTU_LN_LINEAR", "1") != "0"
 
 
-def _ln_uvqk(x, norm_weight, norm_bias, eps, w, kmajor, bias, want_normed):
-    """(uvqk, normed_x or None, mean, rstd): the fused kernel when it takes the shape, else layer norm + GEMM"""
+def _ln_uvqk(x, norm_weight, norm_bias, eps, w, kmajor, bias, want_normed, fp8=None):
+    """(uvqk, normed_x or None, mean, rstd): the fused kernel when it takes the shape, else layer norm + GEMM.  ``fp8``: the
+    weight's (codes, scales) -- the e4m3 kernel; the 16-bit normed_x backward's GEMMs want then comes from the row kernel"""
+    if fp8 is not None:
+        uvqk, _, _, mean, rstd = _launch.ln_linear_fp8_fwd(x, norm_weight, norm_bias, eps, fp8[0], fp8[1], bias)
+        normed_x = _launch.layer_norm_fwd(x, norm_weight, norm_bias, eps)[0] if want_normed else None
+        return uvqk, normed_x, mean, rstd
     if _LN_LINEAR and kmajor and _launch.ln_linear_supported(x, w.shape[0]):
         return _launch.ln_linear_fwd(x, norm_weight, norm_bias, eps, w, bias, want_normed=want_normed)
     normed_x, mean, rstd = _launch.layer_norm_fwd(x, norm_weight, norm_bias, eps)
     return _uvqk_gemm(normed_x, w, kmajor, bias), normed_x, mean, rstd
 
 
-def _recompute_uvqk(x, norm_weight, norm_bias, eps, w, kmajor, bias, normed_x):
+def _recompute_uvqk(x, norm_weight, norm_bias, eps, w, kmajor, bias, normed_x, fp8=None):
     """backward's (uvqk, normed_x) when uvqk was not kept: by the SAME kernel as forward -- the fused kernel and hipBLASLt sum
     in different orders, and a recomputed u that differs from forward's in the last bit makes the one-node and two-node layers
-    disagree -- so where forward took the fused kernel it runs again here even if normed_x was kept (it is the faster call anyway)"""
+    disagree -- so where forward took the fused kernel it runs again here even if normed_x was kept (it is the faster call anyway).
+    ``fp8``: forward's (wq, w_scale) -- the e4m3 kernel again, on the very codes forward multiplied by"""
+    if fp8 is not None:
+        uvqk, nx, _, _ = _ln_uvqk(x, norm_weight, norm_bias, eps, w, kmajor, bias, want_normed=normed_x is None, fp8=fp8)
+        return uvqk, (nx if normed_x is None else normed_x)
     if _LN_LINEAR and kmajor and _launch.ln_linear_supported(x, w.shape[0]):
         uvqk, nx, _, _ = _launch.ln_linear_fwd(x, norm_weight, norm_bias, eps, w, bias, want_normed=normed_x is None)
         return uvqk, (nx if normed_x is None else normed_x)
@@ -393,12 +439,14 @@ class _PreprocessAndAttentionFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, norm_weight, norm_bias, uvqk_weight, uvqk_bias, seq_offsets, num_targets, norm_eps,
                 num_heads, attn_dim, hidden_dim, max_seq_len, attn_alpha, max_attn_len, contextual_seq_len,
-                recompute_uvqk, recompute_normed_x, user_order=None, grad_on=True):
+                recompute_uvqk, recompute_normed_x, user_order=None, grad_on=True, fp8=False):
         ctx.param_dtypes = (norm_weight.dtype, norm_bias.dtype, uvqk_weight.dtype, uvqk_bias.dtype)
+        tracked = grad_on and any(ctx.needs_input_grad)
         (norm_weight, norm_bias, uvqk_weight, uvqk_bias), ctx.kmajor = _prepare_params(
-            (norm_weight, norm_bias, uvqk_weight, uvqk_bias), x.dtype, 2, grad_on and any(ctx.needs_input_grad))
+            (norm_weight, norm_bias, uvqk_weight, uvqk_bias), x.dtype, 2, tracked)
+        fp8w = _fp8_weight(x, uvqk_weight, ctx.kmajor, tracked) if fp8 else None
         uvqk, normed_x, mean, rstd = _ln_uvqk(x, norm_weight, norm_bias, norm_eps, uvqk_weight, ctx.kmajor, uvqk_bias,
-                                              want_normed=not recompute_normed_x)
+                                              want_normed=not recompute_normed_x, fp8=fp8w)
         hv, ha = hidden_dim * num_heads, attn_dim * num_heads
         u_pre = uvqk[:, :hv]
         v = uvqk[:, hv : 2 * hv].view(-1, num_heads, hidden_dim)
@@ -418,6 +466,9 @@ class _PreprocessAndAttentionFunction(torch.autograd.Function):
             saved.append(normed_x)
         if ctx.keep_uvqk:
             saved.append(uvqk)
+        ctx.fp8 = fp8w is not None and not ctx.keep_uvqk      # (the codes serve backward's recompute only)
+        if ctx.fp8:
+            saved.extend(fp8w)
         ctx.save_for_backward(*saved)
         ctx.meta = (norm_eps, num_heads, attn_dim, hidden_dim, max_seq_len, attn_alpha, max_attn_len,
                     contextual_seq_len)
@@ -426,6 +477,7 @@ class _PreprocessAndAttentionFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, du, dout):
         saved = list(ctx.saved_tensors)
+        fp8w = (saved[-2], saved[-1]) if ctx.fp8 else None
         x, nw, nb, mean, rstd, W, beta, seq_offsets = saved[:8]
         rest = saved[8:]
         num_targets = rest.pop(0) if ctx.has_targets else None
@@ -433,7 +485,7 @@ class _PreprocessAndAttentionFunction(torch.autograd.Function):
         uvqk = rest.pop(0) if ctx.keep_uvqk else None
         eps, H, A, Hd, N, alpha, w, c = ctx.meta
         if uvqk is None:
-            uvqk, normed_x = _recompute_uvqk(x, nw, nb, eps, W, ctx.kmajor, beta, normed_x)
+            uvqk, normed_x = _recompute_uvqk(x, nw, nb, eps, W, ctx.kmajor, beta, normed_x, fp8=fp8w)
         elif normed_x is None:
             normed_x, _, _ = _launch.layer_norm_fwd(x, nw, nb, eps)
         hv, ha = Hd * H, A * H
@@ -453,7 +505,7 @@ class _PreprocessAndAttentionFunction(torch.autograd.Function):
         dW = weight_grad_mm(normed_x, duvqk, out_dtype=w_dtype)
         dx, dnw, dnb = _launch.layer_norm_bwd(d_normed, x, nw, mean, rstd)
         return (dx, dnw.to(nw_dtype), dnb.to(nb_dtype), dW, dbeta.to(beta_dtype), None, None, None, None, None, None,
-                None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None)
 
 
 class _STULayerFunction(torch.autograd.Function):
@@ -475,13 +527,14 @@ class _STULayerFunction(torch.autograd.Function):
     def forward(ctx, x, in_nw, in_nb, uvqk_weight, uvqk_bias, out_nw, out_nb, output_weight, seq_offsets, num_targets,
                 in_eps, out_eps, num_heads, attn_dim, hidden_dim, max_seq_len, attn_alpha, max_attn_len, contextual_seq_len,
                 recompute_uvqk, recompute_normed_x, recompute_y, concat_ux, group_norm, dropout_ratio, seed, user_order,
-                grad_on=True):
+                grad_on=True, fp8=False):
         ctx.param_dtypes = tuple(t.dtype for t in (in_nw, in_nb, uvqk_weight, uvqk_bias, out_nw, out_nb, output_weight))
+        tracked = grad_on and any(ctx.needs_input_grad)
         (in_nw, in_nb, uvqk_weight, uvqk_bias, out_nw, out_nb, output_weight), ctx.kmajor = _prepare_params(
-            (in_nw, in_nb, uvqk_weight, uvqk_bias, out_nw, out_nb, output_weight), x.dtype, 2,
-            grad_on and any(ctx.needs_input_grad))
+            (in_nw, in_nb, uvqk_weight, uvqk_bias, out_nw, out_nb, output_weight), x.dtype, 2, tracked)
+        fp8w = _fp8_weight(x, uvqk_weight, ctx.kmajor, tracked) if fp8 else None
         uvqk, normed_x, mean, rstd = _ln_uvqk(x, in_nw, in_nb, in_eps, uvqk_weight, ctx.kmajor, uvqk_bias,
-                                              want_normed=not recompute_normed_x)
+                                              want_normed=not recompute_normed_x, fp8=fp8w)
         hv, ha = hidden_dim * num_heads, attn_dim * num_heads
         v = uvqk[:, hv : 2 * hv].view(-1, num_heads, hidden_dim)
         q = uvqk[:, 2 * hv : 2 * hv + ha].view(-1, num_heads, attn_dim)
@@ -500,6 +553,9 @@ class _STULayerFunction(torch.autograd.Function):
         for keep, t in zip(ctx.keep, (normed_x, uvqk, y)):
             if keep:
                 saved.append(t)
+        ctx.fp8 = fp8w is not None and recompute_uvqk      # (the codes serve backward's recompute only)
+        if ctx.fp8:
+            saved.extend(fp8w)
         ctx.save_for_backward(*saved)
         ctx.user_order = user_order
         ctx.meta = (in_eps, out_eps, num_heads, attn_dim, hidden_dim, max_seq_len, attn_alpha, max_attn_len,
@@ -509,6 +565,7 @@ class _STULayerFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         saved = list(ctx.saved_tensors)
+        fp8w = (saved[-2], saved[-1]) if ctx.fp8 else None
         x, nw, nb, mean, rstd, W, beta, seq_offsets, attn, onw, onb, omean, orstd, Wo = saved[:14]
         rest = saved[14:]
         num_targets = rest.pop(0) if ctx.has_targets else None
@@ -517,7 +574,7 @@ class _STULayerFunction(torch.autograd.Function):
         y = rest.pop(0) if ctx.keep[2] else None
         in_eps, out_eps, H, A, Hd, N, alpha, w, c, cat, gn, p_drop, seed = ctx.meta
         if uvqk is None:
-            uvqk, normed_x = _recompute_uvqk(x, nw, nb, in_eps, W, ctx.kmajor, beta, normed_x)
+            uvqk, normed_x = _recompute_uvqk(x, nw, nb, in_eps, W, ctx.kmajor, beta, normed_x, fp8=fp8w)
         elif normed_x is None:
             normed_x, _, _ = _launch.layer_norm_fwd(x, nw, nb, in_eps)
         hv, ha = Hd * H, A * H
@@ -549,7 +606,7 @@ class _STULayerFunction(torch.autograd.Function):
         d_normed = _uvqk_dgrad(duvqk, W, ctx.kmajor)
         dW = weight_grad_mm(normed_x, duvqk, out_dtype=dt[2])
         dx, dnw, dnb = _launch.layer_norm_bwd(d_normed, x, nw, mean, rstd, dresidual=dout)
-        return (dx, dnw.to(dt[0]), dnb.to(dt[1]), dW, dbeta.to(dt[3]), donw.to(dt[4]), donb.to(dt[5]), dWo) + (None,) * 20
+        return (dx, dnw.to(dt[0]), dnb.to(dt[1]), dW, dbeta.to(dt[3]), donw.to(dt[4]), donb.to(dt[5]), dWo) + (None,) * 21
 
 
 def hstu_fused_layer_applicable(x: torch.Tensor, attn_dim: int, hidden_dim: int) -> bool:
@@ -586,6 +643,7 @@ def hstu_fused_layer(
     recompute_normed_x_in_backward: bool,
     recompute_y_in_backward: bool,
     sort_by_length: bool,
+    fp8_in_addmm_fwd: bool = False,
 ) -> torch.Tensor:
     """``hstu_compute_output(*hstu_preprocess_and_attention(x, ...)[:2], x, ...)`` -- the body of STULayer.forward
     (stu.py:291-352) -- as one autograd node (_STULayerFunction): same arguments, same results.  Not in the
@@ -600,6 +658,8 @@ def hstu_fused_layer(
     torch._assert(hstu_fused_layer_applicable(x, attn_dim, hidden_dim), "head dims must be 16-byte multiples")
     p_drop = float(dropout_ratio) if training else 0.0
     torch._assert(0.0 <= p_drop < 1.0, "dropout_ratio must be in [0, 1)")
+    if fp8_in_addmm_fwd:
+        _fp8_require(x, uvqk_weight.shape[1])
     if x.shape[0] == 0:
         return _empty_rows([(0, x.shape[1])], (x,), (input_norm_weight, input_norm_bias, uvqk_weight, uvqk_bias, output_norm_weight,
                                                      output_norm_bias, output_weight))[0]
@@ -609,7 +669,7 @@ def hstu_fused_layer(
         x, input_norm_weight, input_norm_bias, uvqk_weight, uvqk_bias, output_norm_weight, output_norm_bias, output_weight,
         seq_offsets, num_targets, input_norm_eps, output_norm_eps, num_heads, attn_dim, hidden_dim, max_seq_len, attn_alpha,
         max_attn_len, contextual_seq_len, recompute_uvqk_in_backward, recompute_normed_x_in_backward,
-        recompute_y_in_backward, concat_ux, group_norm, p_drop, seed, order, torch.is_grad_enabled())
+        recompute_y_in_backward, concat_ux, group_norm, p_drop, seed, order, torch.is_grad_enabled(), bool(fp8_in_addmm_fwd))
 
 
 def hstu_preprocess_and_attention(
@@ -634,6 +694,7 @@ def hstu_preprocess_and_attention(
     sort_by_length: bool,
     prefill: bool = False,
     kernel: HammerKernel = HammerKernel.HIP,
+    fp8_in_addmm_fwd: bool = False,
 ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
     torch._assert(max_seq_len > 0, "max_seq_len must be larger than 0")
     torch._assert(x.dim() == 2, "x must be 2-D")
@@ -645,6 +706,8 @@ def hstu_preprocess_and_attention(
     torch._assert(causal is True, "only causal attention is supported.")
     es = x.element_size()
     fusable = (attn_dim * es) % 16 == 0 and (hidden_dim * es) % 16 == 0
+    if fp8_in_addmm_fwd:
+        _fp8_require(x, uvqk_weight.shape[1])
     if x.shape[0] == 0:
         hv, with_kv = hidden_dim * num_heads, prefill or not fusable
         shapes = [(0, hv), (0, hv)] + ([(0, num_heads, attn_dim), (0, num_heads, hidden_dim)] if with_kv else [])
@@ -656,12 +719,12 @@ def hstu_preprocess_and_attention(
             attn_dim, hidden_dim, max_seq_len, attn_alpha, max_attn_len, contextual_seq_len,
             recompute_uvqk_in_backward, recompute_normed_x_in_backward,
             _launch.length_order(_launch._idx(seq_offsets)) if sort_by_length and seq_offsets.numel() > 2 else None,
-            torch.is_grad_enabled(),
+            torch.is_grad_enabled(), bool(fp8_in_addmm_fwd),
         )
         return u, attn_output, None, None
     # prefill (k, v are returned for the KV cache) or head dims that need padding
     u, q, k, v = hstu_compute_uqvk(x, norm_weight, norm_bias, norm_eps, num_heads, attn_dim, hidden_dim,
-                                   uvqk_weight, uvqk_bias)
+                                   uvqk_weight, uvqk_bias, fp8_in_addmm_fwd=fp8_in_addmm_fwd)
     attn_output = hstu_mha(
         max_seq_len=max_seq_len, alpha=attn_alpha, q=q, k=k, v=v, seq_offsets=seq_offsets, causal=causal,
         dropout_pr=0.0, training=False, num_targets=num_targets, max_attn_len=max_attn_len,

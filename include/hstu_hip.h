@@ -295,6 +295,28 @@ int hstu_rms_norm_bwd(const void* dy, const void* x, const void* weight, const f
 int hstu_linear_k512_supported(int64_t rows, int32_t k, int32_t n, int dtype);
 int hstu_linear_k512(const void* x, int64_t ldx, const void* w_nk, const void* bias, void* y, int64_t ldy,
                      int64_t rows, int32_t k, int32_t n, int dtype, void* stream);
+/* Row-wise e4m3 UVQK projection (additive to ABI v13): the reference's fp8_in_addmm_fwd
+ * (ops/cpp/cuda_hstu_preprocess_and_attention.py:75-95,231-245), whose two kernels are outside the open tree.  Arithmetic, with
+ * the convention of hstu_jagged_quantize_fp8 (OCP e4m3fn, round to nearest even, IEEE fp32 divisions):
+ *   nx = LayerNorm(x) ln_w + ln_b  (fp32, not rounded to the I/O type);  x_scale[r] = max_k |nx[r,k]| / 448  (1 for a zero row);
+ *   xq[r,k] = e4m3(clamp(nx[r,k] / x_scale[r], -448, 448));  (wq, w_scale): the (n, k) weight by the same rule, row by row;
+ *   y[r,n] = (sum_k xq[r,k] wq[n,k]) x_scale[r] w_scale[n] + bias[n]   (fp32 accumulation, one rounding to the I/O type).
+ * A row's result depends on no other row of the call.
+ * hstu_quantize_rows_fp8: rows of `src` (bf16 / fp16 / fp32, leading dimension ld in elements) -> dst_q (rows x k bytes,
+ *   contiguous) and scale (fp32 per row); k a multiple of 16 up to 4096 (HSTU_EUNSUPPORTED otherwise); src, its rows and dst_q
+ *   16-byte aligned.
+ * hstu_ln_linear_fp8_fwd: the fused kernel; shape rule and alignment of hstu_ln_linear_fwd (bf16 / fp16, k == 512, n a multiple
+ *   of 32 up to 4096: hstu_ln_linear_fp8_supported; HSTU_EUNSUPPORTED otherwise).  wq: n x 512 bytes; bias (I/O type) may be NULL;
+ *   xq (rows x 512 bytes), x_scale, mean, rstd (fp32 per row) are optional outputs.
+ * hstu_linear_fp8_rowwise: the same kernel without the LayerNorm, on codes and scales (the reference's
+ *   fp8_addmm_fwd_rowwise_fused); xq rows x 512 bytes, contiguous. */
+int hstu_ln_linear_fp8_supported(int64_t rows, int32_t k, int32_t n, int dtype);
+int hstu_quantize_rows_fp8(const void* src, int64_t ld, int64_t rows, int32_t k, int dtype, void* dst_q, float* scale, void* stream);
+int hstu_ln_linear_fp8_fwd(const void* x, int64_t ldx, const void* ln_weight, const void* ln_bias, float eps, const void* wq,
+                           const float* w_scale, const void* bias, void* y, int64_t ldy, void* xq, float* x_scale, float* mean,
+                           float* rstd, int64_t rows, int32_t k, int32_t n, int dtype, void* stream);
+int hstu_linear_fp8_rowwise(const void* xq, const float* x_scale, const void* wq, const float* w_scale, const void* bias, void* y,
+                            int64_t ldy, int64_t rows, int32_t k, int32_t n, int out_dtype, void* stream);
 /* ABI v13: d = a . b + c, row-major, fp32 accumulation, C and D DIFFERENT buffers -- the output stage out = x + y . W_o
  * (`torch.addmm(x, y, output_weight)`, ops/hstu_compute.py:92-136; the reference's own kernel for it: ops/triton/triton_addmm.py:185-340)
  * as ONE hipBLASLt launch.  Through torch.addmm the same product is a copy of x into the result followed by an in-place GEMM with
