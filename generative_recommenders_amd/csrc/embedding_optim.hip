@@ -29,38 +29,35 @@
 // list a data-parallel rank exchanges (ops/embedding.py).  The rank comes from an inclusive scan over the head flags of the
 // sorted positions (three small kernels in front of the chunk kernel); the sums are the update's, addition for addition.
 //
-// A table stored in 16 bits (fp16 / bf16; hstu_embedding_rowwise_adagrad_lowp) is a second element type of the same
-// kernels (ApplySink16): its prefetched rows stay in their raw 16-bit form, half the registers, until the segment ends;
-// there the row is widened to fp32, updated by apply_update's arithmetic -- the fp32 result equals the fp32 table's bit for
-// bit -- and written back through the stochastic rounding of stochastic_round.h, whose random bits are a function of
-// (seed, table row, column) alone.  momentum1 stays fp32.
+// Every table update -- row-wise Adagrad, sparse SGD and sparse Adam (hstu_embedding_sparse_sgd / hstu_embedding_sparse_adam;
+// the other two choices of the reference's sparse_optimizer_factory_and_class), each on fp32, fp16 or bf16 tables -- is ONE
+// sink, UpdateSink<W, Rule>: W the table's element type, Rule what the optimizer alone knows.  The sink owns what they share:
+// the table row travels with the group of gradient rows (its Pre record; a 16-bit table's row in its raw form, half the
+// registers), and at the segment's end it is widened to fp32 piece by piece, run through the rule's element function, and
+// written back -- an fp32 table's into the row's own registers and out with one row store, a 16-bit table's through the
+// stochastic rounding of stochastic_round.h, whose random bits are a function of (seed, table row, column) alone.  A rule
+// names the scalars that travel too (Adagrad: momentum1[r]), what it does once per row (Adagrad: the row's sum of squares,
+// momentum1[r], the step), and the arithmetic of one element (adagrad_element, sgd_element, adam_element): the same function
+// for every table type and for both kernels, its multiply-adds pinned by fmaf, so a 16-bit table's fp32 row and state equal
+// the fp32 table's bit for bit.  Adam's rule prefetches NOTHING and reads exp_avg / exp_avg_sq of the row where the segment
+// ends, piece by piece: prefetched like the table row they would be 128 more registers at the reference's row width (dim 256,
+// 16-bit gradients, eight rows in flight: 8 + 32 + 64 are held already), which leaves the wave alone on its SIMD, while the
+// loads at the segment's end are hidden by the other waves the smaller kernel leaves room for.
 //
-// Sparse SGD and sparse Adam (hstu_embedding_sparse_sgd / hstu_embedding_sparse_adam; the other two choices of the reference's
-// sparse_optimizer_factory_and_class) are two more endings of the same walk: SgdSink<W> and AdamSink<W>, W the table's element
-// type.  What travels with a group of gradient rows is the sink's business (its Pre record, prefetch / finish): Adagrad
-// the table row and its scalar, SGD the table row, the coalesce its slot.  Adam prefetches the table row ONLY and reads
-// exp_avg / exp_avg_sq of the row where the segment ends: prefetched like the table row they would be 128 more registers at
-// the reference's row width (dim 256, 16-bit gradients, eight rows in flight: 8 + 32 + 64 are held already), which leaves
-// the wave alone on its SIMD, while the loads at the segment's end are hidden by the other waves the smaller kernel leaves
-// room for.  The arithmetic of one element (adam_element, sgd_element) is the same function for every table type and for
-// both kernels, its multiply-adds pinned by fmaf, so a 16-bit table's fp32 row, exp_avg and exp_avg_sq equal the fp32 table's.
+// What the host decides -- chunk size, row class, workspace layouts, grids, LDS bytes, the widest row of every entry point --
+// is embedding_optim_dispatch.h, host-only and swept by a CPU test; this unit compiles exactly the classes it can return.
+#include <utility>
+
 #include "hstu_common.cuh"
 #include "capi_internal.h"
+#include "embedding_optim_dispatch.h"
 #include "embedding_sort.cuh"
 #include "row_pass.cuh"
 #include "stochastic_round.h"
 
 namespace hstu {
 
-constexpr int kOptWaves = 4;
-constexpr int kChunkLarge = 128;       // sorted rows per wave of the chunk kernel: two coalesced loads of the (id, row) pairs
-constexpr int kChunkSmall = 32;        // below kSmallBatch ids: four times the waves, a quarter of the groups each walks
-constexpr int64_t kSmallBatch = 262144;
-constexpr int kSmallChunkMaxDim = 512; // four times the partial sums of a quarter of the widest row: the same workspace
-constexpr int kCombineWaves = 8;       // waves that share one cut segment's partial sums
-constexpr int kOptMaxPieces = 4;       // 16-byte pieces per lane and dout row: rows of up to 4 KiB
-constexpr int kOptMaxDim = 2048;       // 4 KiB of bf16 / fp16: the widest partial sum (8 KiB of fp32)
-constexpr int kOptMaxBlocks = 8192;    // grid-stride above this
+using namespace embedding_optim;
 
 // acc[j][c]: column (lane + 64 j) * VEC + c of the row; pieces = dim / VEC of them are real
 template <int VEC, int NP>
@@ -140,22 +137,6 @@ __device__ __forceinline__ float row_sum_of_squares(const float (&acc)[NP][VEC],
 #pragma unroll
   for (int off = 32; off >= (VEC == 4 ? 2 : 1); off >>= 1) ss += __shfl_xor(ss, off);
   return ss;
-}
-
-// the update of one finished segment: acc = G[r, :], w = W[r, :] (loaded by the caller ahead of time), m_old =
-// momentum1[r].
-template <int VEC, int NP>
-__device__ __forceinline__ void apply_update(const float (&acc)[NP][VEC], float (&w)[NP][VEC], float m_old, int lane, int pieces, int dim,
-                                             float* __restrict__ w_row, float* __restrict__ m_ptr, float lr, float eps) {
-  const float ss = row_sum_of_squares<VEC, NP>(acc, lane, pieces);
-  const float m_new = m_old + ss / (float)dim;
-  const float step = lr / (sqrtf(m_new) + eps);
-#pragma unroll
-  for (int j = 0; j < NP; ++j)
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) w[j][c] -= step * acc[j][c];
-  store_f32_row<VEC, NP>(w_row, lane, pieces, w);
-  if (lane == 0) *m_ptr = m_new;
 }
 
 // The registers a prefetched table row waits in: fp32 as loaded, or the raw 16-bit elements, two per register (VEC / 2
@@ -251,129 +232,63 @@ __device__ __forceinline__ void widen_piece(const typename WRow<WT, VEC, NP>::ty
     for (int c = 0; c < VEC; ++c) x[c] = w[j][c];
   }
 }
-// ... and piece p of table row `id` written back: as it is, or every element rounded with its own 16 random bits -- one hash per
+// ... and piece p of row `id` of a 16-bit table written back: every element rounded with its own 16 random bits -- one hash per
 // column pair (round_piece)
 template <typename WT, int VEC>
 __device__ __forceinline__ void write_piece(WT* __restrict__ w_row, int p, const float (&x)[VEC], uint64_t seed, int id) {
-  if constexpr (sizeof(WT) == 2) {
-    uint32_t out[VEC / 2];
-    round_piece<WT, VEC>(x, seed, (uint32_t)id, (uint32_t)(p * (VEC / 2)), out);
-    if constexpr (VEC == 8) *(u32x4*)(w_row + (int64_t)p * VEC) = *(const u32x4*)&out[0];
-    else *(u32x2*)(w_row + (int64_t)p * VEC) = *(const u32x2*)&out[0];
-  } else {
-#pragma unroll
-    for (int c = 0; c < VEC; c += 4) *(float4*)(w_row + (int64_t)p * VEC + c) = *(const float4*)&x[c];
-  }
+  static_assert(sizeof(WT) == 2, "an fp32 row goes back into its own registers (UpdateSink::finish)");
+  uint32_t out[VEC / 2];
+  round_piece<WT, VEC>(x, seed, (uint32_t)id, (uint32_t)(p * (VEC / 2)), out);
+  if constexpr (VEC == 8) *(u32x4*)(w_row + (int64_t)p * VEC) = *(const u32x4*)&out[0];
+  else *(u32x2*)(w_row + (int64_t)p * VEC) = *(const u32x2*)&out[0];
 }
 
 // What the chunk and combine kernels do with a finished segment is their Sink.  A sink names what travels with a group of
 // gradient rows for every segment that ends in the group (Pre, filled by prefetch: table row `id`, whose segment ends at the
-// sorted position `pos`) and what happens at the segment's end (finish: acc = G[id, :]).
+// sorted position `pos`) and what happens at the segment's end (finish: acc = G[id, :]).  It states kApplies (it updates a
+// table: the header's row classes differ) and kRounds (finish rounds a 16-bit row: the combine kernel makes room for that).
+// An optimizer's Rule: Pre, the scalars that travel with the table row (prefetch); begin, once per finished row, whose result
+// every piece gets; piece, the element function over one piece p of the row -- g = G[id, piece p], x = W[id, piece p] in fp32.
 //
-// Row-wise Adagrad on an fp32 table: the table row and momentum1[id] travel ...
-struct ApplySink {
-  static constexpr bool kApply = true;
-  typedef float WT;
-  float *weight, *momentum1;
-  float lr, eps;
-  template <int VEC, int NP>
-  struct Pre {
-    float w[NP][VEC];
-    float m_old = 0.f;
-  };
-  template <int VEC, int NP>
-  __device__ __forceinline__ void prefetch(Pre<VEC, NP>& pre, int id, int64_t pos, int lane, int pieces, int dim) const {
-    load_w_row<VEC, NP>(weight + (int64_t)id * dim, lane, pieces, pre.w);
-    pre.m_old = momentum1[id];
-  }
-  template <int VEC, int NP>
-  __device__ __forceinline__ void finish(const float (&acc)[NP][VEC], Pre<VEC, NP>& pre, int id, int lane, int pieces, int dim) const {
-    apply_update<VEC, NP>(acc, pre.w, pre.m_old, lane, pieces, dim, weight + (int64_t)id * dim, momentum1 + id, lr, eps);
-  }
-};
-// ... on a table of 16-bit rows (W: f16_t or bf16_t): apply_update's arithmetic on the widened row (the multiply-add
-// contracted as the compiler contracts it there, pinned by fmaf), written back by stochastic rounding ...
-template <typename W>
-struct ApplySink16 {
-  static constexpr bool kApply = true;
-  typedef W WT;
-  W* weight;
+// Row-wise Adagrad: momentum1[id] travels; the row's step comes from the sum of squares of G[id, :] ...
+__device__ __forceinline__ float adagrad_element(float g, float w, float step) { return fmaf(-step, g, w); }
+
+struct AdagradRule {
   float* momentum1;
   float lr, eps;
-  uint64_t seed;
-  template <int VEC, int NP>
   struct Pre {
-    uint32_t w[NP][VEC / 2];
     float m_old = 0.f;
   };
+  __device__ __forceinline__ void prefetch(Pre& s, int id) const { s.m_old = momentum1[id]; }
   template <int VEC, int NP>
-  __device__ __forceinline__ void prefetch(Pre<VEC, NP>& pre, int id, int64_t pos, int lane, int pieces, int dim) const {
-    load_w_row<VEC, NP>(weight + (int64_t)id * dim, lane, pieces, pre.w);
-    pre.m_old = momentum1[id];
-  }
-  template <int VEC, int NP>
-  __device__ __forceinline__ void finish(const float (&acc)[NP][VEC], Pre<VEC, NP>& pre, int id, int lane, int pieces, int dim) const {
+  __device__ __forceinline__ float begin(const float (&acc)[NP][VEC], const Pre& s, int id, int lane, int pieces, int dim) const {
     const float ss = row_sum_of_squares<VEC, NP>(acc, lane, pieces);
-    const float m_new = pre.m_old + ss / (float)dim;
-    const float step = lr / (sqrtf(m_new) + eps);
-    W* __restrict__ w_row = weight + (int64_t)id * dim;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-      const int p = lane + 64 * j;
-      if (p < pieces) {
-        float x[VEC];
-#pragma unroll
-        for (int c = 0; c < VEC / 2; ++c) {
-          x[2 * c] = fmaf(-step, acc[j][2 * c], widen16<W>(pre.w[j][c] & 0xffffu));
-          x[2 * c + 1] = fmaf(-step, acc[j][2 * c + 1], widen16<W>(pre.w[j][c] >> 16));
-        }
-        write_piece<W, VEC>(w_row, p, x, seed, id);
-      }
-    }
+    const float m_new = s.m_old + ss / (float)dim;
     if (lane == 0) momentum1[id] = m_new;
+    return lr / (sqrtf(m_new) + eps);
+  }
+  template <int VEC>
+  __device__ __forceinline__ void piece(const float (&g)[VEC], float (&x)[VEC], float step, int p) const {
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) x[c] = adagrad_element(g[c], x[c], step);
   }
 };
 
-// ... SGD, W[r, :] -= lr * G[r, :], on a table of fp32 or 16-bit rows (WT: float, f16_t or bf16_t): the table row travels ...
+// ... SGD, W[r, :] -= lr * G[r, :]: nothing but the table row travels ...
 __device__ __forceinline__ float sgd_element(float g, float w, float lr) { return fmaf(-lr, g, w); }
 
-template <typename W>
-struct SgdSink {
-  static constexpr bool kApply = true;
-  typedef W WT;
-  W* weight;
+struct SgdRule {
   float lr;
-  uint64_t seed;
+  struct Pre {};
+  __device__ __forceinline__ void prefetch(Pre&, int) const {}
   template <int VEC, int NP>
-  struct Pre {
-    typename WRow<W, VEC, NP>::type w;
-  };
-  template <int VEC, int NP>
-  __device__ __forceinline__ void prefetch(Pre<VEC, NP>& pre, int id, int64_t pos, int lane, int pieces, int dim) const {
-    load_w_row<VEC, NP>(weight + (int64_t)id * dim, lane, pieces, pre.w);
+  __device__ __forceinline__ float begin(const float (&)[NP][VEC], const Pre&, int, int, int, int) const {
+    return lr;
   }
-  template <int VEC, int NP>
-  __device__ __forceinline__ void finish(const float (&acc)[NP][VEC], Pre<VEC, NP>& pre, int id, int lane, int pieces, int dim) const {
-    W* __restrict__ w_row = weight + (int64_t)id * dim;
-    if constexpr (sizeof(W) == 4) {                 // in the prefetched row's own registers, stored as apply_update stores it
+  template <int VEC>
+  __device__ __forceinline__ void piece(const float (&g)[VEC], float (&x)[VEC], float lr_, int p) const {
 #pragma unroll
-      for (int j = 0; j < NP; ++j)
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) pre.w[j][c] = sgd_element(acc[j][c], pre.w[j][c], lr);
-      store_f32_row<VEC, NP>(w_row, lane, pieces, pre.w);
-    } else {
-#pragma unroll
-      for (int j = 0; j < NP; ++j) {
-        const int p = lane + 64 * j;
-        if (p < pieces) {
-          float x[VEC];
-          widen_piece<W, VEC, NP>(pre.w, j, x);
-#pragma unroll
-          for (int c = 0; c < VEC; ++c) x[c] = sgd_element(acc[j][c], x[c], lr);
-          write_piece<W, VEC>(w_row, p, x, seed, id);
-        }
-      }
-    }
+    for (int c = 0; c < VEC; ++c) x[c] = sgd_element(g[c], x[c], lr_);
   }
 };
 
@@ -391,56 +306,82 @@ __device__ __forceinline__ float adam_element(float g, float& m, float& v, float
   return w - (k.step_size * m) / (sqrtf(v) / k.sqrt_bc2 + k.eps);
 }
 
-// The table row travels with the gradient rows; exp_avg[id, :] and exp_avg_sq[id, :] are read where the segment ends, piece by
-// piece (see the head of this file for why)
-template <typename W>
-struct AdamSink {
-  static constexpr bool kApply = true;
-  typedef W WT;
-  W* weight;
+// Nothing but the table row travels: exp_avg[id, :] and exp_avg_sq[id, :] are read where the segment ends, piece by piece (see
+// the head of this file for why).  The row hands its pieces row `id` of the two state tensors.  (Two pointers formed once per row, not
+// an offset added per piece: with that the kernels of two and more pieces take some 20 more registers, and several lose a
+// wave per SIMD.)
+struct AdamRule {
   float *exp_avg, *exp_avg_sq;
   AdamCoef k;
+  struct Pre {};
+  struct Row {
+    float *m, *v;
+  };
+  __device__ __forceinline__ void prefetch(Pre&, int) const {}
+  template <int VEC, int NP>
+  __device__ __forceinline__ Row begin(const float (&)[NP][VEC], const Pre&, int id, int, int, int dim) const {
+    return Row{exp_avg + (int64_t)id * dim, exp_avg_sq + (int64_t)id * dim};
+  }
+  template <int VEC>
+  __device__ __forceinline__ void piece(const float (&g)[VEC], float (&x)[VEC], const Row& row, int p) const {
+    float* m_at = row.m + (int64_t)p * VEC;
+    float* v_at = row.v + (int64_t)p * VEC;
+    float m[VEC], v[VEC];
+#pragma unroll
+    for (int c = 0; c < VEC; c += 4) {
+      *(float4*)&m[c] = *(const float4*)(m_at + c);
+      *(float4*)&v[c] = *(const float4*)(v_at + c);
+    }
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) x[c] = adam_element(g[c], m[c], v[c], x[c], k);
+#pragma unroll
+    for (int c = 0; c < VEC; c += 4) {
+      *(float4*)(m_at + c) = *(const float4*)&m[c];
+      *(float4*)(v_at + c) = *(const float4*)&v[c];
+    }
+  }
+};
+
+// The update of a table of W (float, f16_t or bf16_t) by Rule: the table row and the rule's scalars travel; at the segment's
+// end every piece is widened, updated and written back.  The one place where the table types part: an fp32 row goes back into
+// its own registers and out with one row store, a 16-bit row through write_piece's stochastic rounding with `seed`.
+template <typename W, typename Rule>
+struct UpdateSink {
+  static constexpr bool kApplies = true;
+  static constexpr bool kRounds = sizeof(W) == 2;
+  W* weight;
+  Rule rule;
   uint64_t seed;
   template <int VEC, int NP>
   struct Pre {
     typename WRow<W, VEC, NP>::type w;
+    typename Rule::Pre s;
   };
   template <int VEC, int NP>
   __device__ __forceinline__ void prefetch(Pre<VEC, NP>& pre, int id, int64_t pos, int lane, int pieces, int dim) const {
     load_w_row<VEC, NP>(weight + (int64_t)id * dim, lane, pieces, pre.w);
+    rule.prefetch(pre.s, id);
   }
   template <int VEC, int NP>
   __device__ __forceinline__ void finish(const float (&acc)[NP][VEC], Pre<VEC, NP>& pre, int id, int lane, int pieces, int dim) const {
     W* __restrict__ w_row = weight + (int64_t)id * dim;
-    float* __restrict__ m_row = exp_avg + (int64_t)id * dim;
-    float* __restrict__ v_row = exp_avg_sq + (int64_t)id * dim;
+    const auto row = rule.template begin<VEC, NP>(acc, pre.s, id, lane, pieces, dim);
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
       const int p = lane + 64 * j;
       if (p < pieces) {
-        float x[VEC], m[VEC], v[VEC];
-#pragma unroll
-        for (int c = 0; c < VEC; c += 4) {
-          *(float4*)&m[c] = *(const float4*)(m_row + (int64_t)p * VEC + c);
-          *(float4*)&v[c] = *(const float4*)(v_row + (int64_t)p * VEC + c);
-        }
+        float x[VEC];
         widen_piece<W, VEC, NP>(pre.w, j, x);
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) x[c] = adam_element(acc[j][c], m[c], v[c], x[c], k);
-#pragma unroll
-        for (int c = 0; c < VEC; c += 4) {
-          *(float4*)(m_row + (int64_t)p * VEC + c) = *(const float4*)&m[c];
-          *(float4*)(v_row + (int64_t)p * VEC + c) = *(const float4*)&v[c];
-        }
-        if constexpr (sizeof(W) == 4) {             // back into the prefetched row's own registers, stored below as apply_update stores it
+        rule.template piece<VEC>(acc[j], x, row, p);
+        if constexpr (kRounds) {
+          write_piece<W, VEC>(w_row, p, x, seed, id);
+        } else {
 #pragma unroll
           for (int c = 0; c < VEC; ++c) pre.w[j][c] = x[c];
-        } else {
-          write_piece<W, VEC>(w_row, p, x, seed, id);
         }
       }
     }
-    if constexpr (sizeof(W) == 4) store_f32_row<VEC, NP>(w_row, lane, pieces, pre.w);
+    if constexpr (!kRounds) store_f32_row<VEC, NP>(w_row, lane, pieces, pre.w);
   }
 };
 
@@ -448,8 +389,8 @@ struct AdamSink {
 // segment heads among the sorted positions 0 .. p, the same for every position of a segment, so any of them names the
 // segment's slot rank[p] - 1, which travels
 struct EmitSink {
-  static constexpr bool kApply = false;
-  typedef float WT;
+  static constexpr bool kApplies = false;
+  static constexpr bool kRounds = false;
   int32_t* rows;
   float* G;
   const int32_t* rank;
@@ -614,7 +555,7 @@ __global__ __launch_bounds__(kCombineWaves * 64) void optim_combine_kernel(const
     __syncthreads();
     if (wave == 0) {
       // eight pieces: one share at a time, or the row's registers spill; so do four next to a 16-bit table's rounding
-      constexpr int kShareUnroll = NP >= 8 || (NP >= 4 && sizeof(typename Sink::WT) == 2) ? 1 : kCombineWaves - 1;
+      constexpr int kShareUnroll = NP >= 8 || (NP >= 4 && Sink::kRounds) ? 1 : kCombineWaves - 1;
 #pragma unroll kShareUnroll
       for (int s = 0; s < kCombineWaves - 1; ++s) {
         float v[NP][VEC];
@@ -630,11 +571,6 @@ __global__ __launch_bounds__(kCombineWaves * 64) void optim_combine_kernel(const
 // ---- the coalesce's slots: rank[p] = number of segment heads among the sorted positions 0 .. p (an inclusive scan of the
 // head flags; integers, so any order gives the same result).  Tiles of kScanTile positions: count the heads per tile,
 // scan the tile counts in one workgroup (which also knows the total: *count), scan every tile from its offset.
-constexpr int kScanThreads = 256;
-constexpr int kScanItems = 8;          // consecutive positions per thread: two 16-byte stores of ranks
-constexpr int kScanTile = kScanThreads * kScanItems;
-constexpr int kTileScanThreads = 1024;
-
 // exclusive scan of one value per thread across the workgroup (THREADS / 64 waves); total: the sum, in every thread
 template <int THREADS>
 __device__ __forceinline__ int block_exclusive_scan(int v, int* wave_sums, int& total) {
@@ -723,95 +659,54 @@ __global__ __launch_bounds__(kScanThreads) void head_rank_kernel(const int32_t* 
   }
 }
 
-struct OptLayout {
-  size_t part, partials_off, temp_off, temp_bytes, total;
-};
-
-// Small chunks for small batches, where the partial sums (packed at the row's own width) still fit the room laid out below:
-// 2 * ceil(n / 32) * dim <= 2 * 4 * ceil(n / 128) * (kOptMaxDim / 4) for dim <= kSmallChunkMaxDim.
-static int opt_chunk(int64_t n, int dim) { return n < kSmallBatch && dim <= kSmallChunkMaxDim ? kChunkSmall : kChunkLarge; }
-static_assert(kChunkLarge / kChunkSmall * kSmallChunkMaxDim <= kOptMaxDim, "the small chunks' partial sums must fit the workspace");
-
-// sorted_idx | perm (n each) | partial sums (two per 128 positions, sized for the widest row: dim is not known here, and the
-// size must not depend on it) | sort temporary
-static OptLayout opt_layout(int64_t n, int table_rows) {
-  OptLayout l;
-  l.part = align256((size_t)n * sizeof(int32_t));
-  l.partials_off = 2 * l.part;
-  l.temp_off = l.partials_off + align256(2 * (size_t)((n + kChunkLarge - 1) / kChunkLarge) * kOptMaxDim * sizeof(float));
-  l.temp_bytes = n ? sort_temp_bytes(n, table_rows) : 0;
-  l.total = l.temp_off + align256(l.temp_bytes);
-  return l;
-}
-
-// the update's workspace | rank (n) | heads per scan tile
-struct CoalesceLayout {
-  OptLayout opt;
-  size_t rank_off, tiles_off, total;
-};
-
-static CoalesceLayout coalesce_layout(int64_t n, int table_rows) {
-  CoalesceLayout l;
-  l.opt = opt_layout(n, table_rows);
-  l.rank_off = l.opt.total;
-  l.tiles_off = l.rank_off + align256((size_t)n * sizeof(int32_t));
-  l.total = l.tiles_off + align256((size_t)((n + kScanTile - 1) / kScanTile) * sizeof(int32_t));
-  return l;
-}
-
-static int launch_head_ranks(const int32_t* sorted_idx, int64_t n, int32_t* tile_heads, int32_t* rank, int32_t* count, hipStream_t st,
-                             const char* what) {
-  const int64_t tiles = (n + kScanTile - 1) / kScanTile;
-  const dim3 grid((unsigned)(tiles < kOptMaxBlocks ? tiles : kOptMaxBlocks));
-  hipLaunchKernelGGL(head_count_kernel, grid, dim3(kScanThreads), 0, st, sorted_idx, n, tiles, tile_heads);
-  if (int rc = check_launch(what)) return rc;
-  hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(kTileScanThreads), 0, st, tile_heads, tiles, count);
-  if (int rc = check_launch(what)) return rc;
-  hipLaunchKernelGGL(head_rank_kernel, grid, dim3(kScanThreads), 0, st, sorted_idx, n, tiles, (const int32_t*)tile_heads, rank);
-  return check_launch(what);
-}
-
+// what the kernels walk: the gradient rows and the carved workspace (rank, tile_heads: the coalesce's)
 struct OptArgs {
   const void* g;
   const int32_t *perm, *sorted_idx;
   int64_t n;
   int dim;
   float* partials;
+  int32_t *rank, *tile_heads;
   hipStream_t st;
 };
 
-template <typename T, int NP, int U, int kChunk, typename Sink>
-static int opt_launch_chunk(const OptArgs& a, const Sink& sink, const char* what) {
-  constexpr int VEC = 16 / (int)sizeof(T);
-  const int64_t chunks = (a.n + kChunk - 1) / kChunk;
-  const int64_t blocks = (chunks + kOptWaves - 1) / kOptWaves;
-  hipLaunchKernelGGL((optim_chunk_kernel<T, NP, U, kChunk, Sink>), dim3((unsigned)(blocks < kOptMaxBlocks ? blocks : kOptMaxBlocks)),
-                     dim3(kOptWaves * 64), 0, a.st, (const T*)a.g, a.perm, a.sorted_idx, a.n, a.dim, a.partials, sink);
+static int launch_head_ranks(const OptArgs& a, const Plan& p, int32_t* count, const char* what) {
+  const dim3 grid((unsigned)p.scan_grid);
+  hipLaunchKernelGGL(head_count_kernel, grid, dim3(kScanThreads), 0, a.st, a.sorted_idx, a.n, p.scan_tiles, a.tile_heads);
   if (int rc = check_launch(what)) return rc;
-  if (chunks < 2) return HSTU_OK;                                          // one chunk: nothing can leave it
-  const size_t lds = (size_t)(kCombineWaves - 1) * a.dim * sizeof(float);  // at most 56 KiB
-  hipLaunchKernelGGL((optim_combine_kernel<VEC, NP, kChunk, Sink>), dim3((unsigned)(chunks - 1 < kOptMaxBlocks ? chunks - 1 : kOptMaxBlocks)),
-                     dim3(kCombineWaves * 64), lds, a.st, a.sorted_idx, a.n, a.dim, a.partials, sink);
+  hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(kTileScanThreads), 0, a.st, a.tile_heads, p.scan_tiles, count);
+  if (int rc = check_launch(what)) return rc;
+  hipLaunchKernelGGL(head_rank_kernel, grid, dim3(kScanThreads), 0, a.st, a.sorted_idx, a.n, p.scan_tiles, (const int32_t*)a.tile_heads,
+                     a.rank);
   return check_launch(what);
 }
 
-template <typename T, int NP, int U, typename Sink>
-static int opt_launch(const OptArgs& a, const Sink& sink, const char* what) {
-  return opt_chunk(a.n, a.dim) == kChunkSmall ? opt_launch_chunk<T, NP, U, kChunkSmall>(a, sink, what)
-                                              : opt_launch_chunk<T, NP, U, kChunkLarge>(a, sink, what);
+// The class (T, NP, U, kChunk) of the plan's kernels, compiled where the plan can name it and nowhere else; true: it was p's
+template <typename T, int NP, int U, int kChunk, typename Sink>
+static bool opt_launch(const OptArgs& a, const Plan& p, const Sink& sink, const char* what, int* rc) {
+  if constexpr (reachable((int)sizeof(T), NP, U, kChunk, Sink::kApplies)) {
+    if (p.np != NP || p.u != U || p.chunk != kChunk) return false;
+    constexpr int VEC = 16 / (int)sizeof(T);
+    hipLaunchKernelGGL((optim_chunk_kernel<T, NP, U, kChunk, Sink>), dim3((unsigned)p.chunk_grid), dim3(kOptWaves * 64), 0, a.st,
+                       (const T*)a.g, a.perm, a.sorted_idx, a.n, a.dim, a.partials, sink);
+    *rc = check_launch(what);
+    if (*rc || !p.combine_grid) return true;
+    hipLaunchKernelGGL((optim_combine_kernel<VEC, NP, kChunk, Sink>), dim3((unsigned)p.combine_grid), dim3(kCombineWaves * 64),
+                       p.combine_lds, a.st, a.sorted_idx, a.n, a.dim, a.partials, sink);
+    *rc = check_launch(what);
+    return true;
+  }
+  return false;
 }
 
-// gradient rows in flight per wave: eight for rows of up to 1 KiB (the reference's dim 256 in any dtype), fewer for wider
-// rows -- each comes with a table row of twice (16-bit dout) or once its size in registers
-// (the coalesce keeps them: the groups do not change the order of a sum, and one rule is one thing less to test)
-template <typename T, typename Sink>
-static int opt_dispatch(const OptArgs& a, const Sink& sink, const char* what) {
-  const int row_bytes = a.dim * (int)sizeof(T);
-  if (row_bytes <= 1024) return opt_launch<T, 1, 8>(a, sink, what);
-  if (row_bytes <= 2048) return opt_launch<T, 2, 4>(a, sink, what);
-  if constexpr (sizeof(T) == 4 && Sink::kApply)     // coalesced fp32 rows of tables wider than 1024 columns: 8 KiB
-    if (row_bytes > 4096) return opt_launch<T, 8, 2>(a, sink, what);
-  return opt_launch<T, 4, (sizeof(T) == 2 ? 2 : 4)>(a, sink, what);
+// every row class of the header at both chunk sizes: the first that is the plan's launches (row_class returns no other)
+template <typename T, typename Sink, size_t... I>
+static int opt_dispatch(const OptArgs& a, const Sink& sink, const char* what, std::index_sequence<I...>) {
+  const Plan p = plan((int)sizeof(T), a.dim, a.n, Sink::kApplies);
+  int rc = HSTU_OK;
+  (void)((opt_launch<T, kRowClasses[I].np, kRowClasses[I].u, kChunkSmall>(a, p, sink, what, &rc) ||
+          opt_launch<T, kRowClasses[I].np, kRowClasses[I].u, kChunkLarge>(a, p, sink, what, &rc)) || ...);
+  return rc;
 }
 
 // hstu_stochastic_round: one wave per row (grid-stride), lanes own 16-byte pieces of the 16-bit row (VEC = 8; VEC = 1 for
@@ -840,12 +735,25 @@ __global__ __launch_bounds__(kSrWaves * 64) void stochastic_round_kernel(const f
 
 template <typename Sink>
 static int opt_dispatch_dtype(int dtype, const OptArgs& a, const Sink& sink, const char* what) {
+  constexpr auto classes = std::make_index_sequence<sizeof(kRowClasses) / sizeof(kRowClasses[0])>{};
   switch (dtype) {
-    case HSTU_DTYPE_BF16: return opt_dispatch<bf16_t>(a, sink, what);
-    case HSTU_DTYPE_F16: return opt_dispatch<f16_t>(a, sink, what);
-    default: return opt_dispatch<float>(a, sink, what);
+    case HSTU_DTYPE_BF16: return opt_dispatch<bf16_t>(a, sink, what, classes);
+    case HSTU_DTYPE_F16: return opt_dispatch<f16_t>(a, sink, what, classes);
+    default: return opt_dispatch<float>(a, sink, what, classes);
   }
 }
+
+// an update's sink for the table's element type: UpdateSink<float | f16_t | bf16_t, Rule> (an fp32 table is not rounded: seed 0)
+template <typename Rule>
+static int update_dispatch(int weight_dtype, void* weight, const Rule& rule, uint64_t seed, int dtype, const OptArgs& a, const char* what) {
+  switch (weight_dtype) {
+    case HSTU_DTYPE_F16: return opt_dispatch_dtype(dtype, a, UpdateSink<f16_t, Rule>{(f16_t*)weight, rule, seed}, what);
+    case HSTU_DTYPE_BF16: return opt_dispatch_dtype(dtype, a, UpdateSink<bf16_t, Rule>{(bf16_t*)weight, rule, seed}, what);
+    default: return opt_dispatch_dtype(dtype, a, UpdateSink<float, Rule>{(float*)weight, rule, 0}, what);
+  }
+}
+
+static size_t sort_temp(int64_t n, int table_rows) { return n ? sort_temp_bytes(n, table_rows) : 0; }
 
 }  // namespace hstu
 
@@ -856,13 +764,21 @@ extern "C" {
 int hstu_embedding_rowwise_adagrad_workspace_bytes(int64_t n, int32_t table_rows, int64_t* bytes) {
   if (!bytes || n < 0 || n > 0x7fffffffLL || table_rows <= 0)
     return set_error(HSTU_EINVAL, "hstu_embedding_rowwise_adagrad_workspace_bytes: bad arguments");
-  *bytes = (int64_t)opt_layout(n, table_rows).total;
+  *bytes = (int64_t)opt_layout(n, sort_temp(n, table_rows)).total;
   return HSTU_OK;
 }
 
-// What every update's entry point takes, and the part they share: the checks and the sort.  max_row_bytes: the widest dout row
-// the entry point takes; weight_dtype: fp32, or a 16-bit table written back by stochastic rounding; state_ok: the optimizer's
-// state tensors (named in `tensors` with the weight) are there.  *go is false when there is nothing to launch.
+int hstu_embedding_grad_coalesce_workspace_bytes(int64_t n, int32_t table_rows, int64_t* bytes) {
+  if (!bytes || n < 0 || n > 0x7fffffffLL || table_rows <= 0)
+    return set_error(HSTU_EINVAL, "hstu_embedding_grad_coalesce_workspace_bytes: bad arguments");
+  *bytes = (int64_t)coalesce_layout(n, sort_temp(n, table_rows)).total;
+  return HSTU_OK;
+}
+
+// What every entry point that walks gradient rows takes, and the part they share: the checks, the carving of the workspace
+// and the sort.  max_row_bytes: the widest dout row the entry point takes; out: the rows it writes with 16-byte stores (the
+// table, or the coalesce's G); weight_dtype: fp32, or a 16-bit table written back by stochastic rounding; coalesce: the
+// workspace is the coalesce's (rank and scan tiles behind the update's).
 struct SparseCall {
   const char* what;
   int max_row_bytes;
@@ -870,65 +786,64 @@ struct SparseCall {
   const int32_t* idx;
   int64_t n;
   int32_t dim, table_rows;
-  void* weight;
+  void* out;
   int weight_dtype;
   void* workspace;
   int64_t workspace_bytes;
   int dtype;
   void* stream;
+  bool coalesce;
 };
 
-static int sparse_update_begin(const SparseCall& c, bool state_ok, const char* tensors, OptArgs* a, bool* go) {
+// required_ok: the pointers named in `required` are there (checked first); outputs_ok: those that only a non-empty batch
+// needs.  *go is false when there is nothing to launch.
+static int sparse_begin(const SparseCall& c, bool required_ok, const char* required, bool outputs_ok, OptArgs* a, bool* go) {
   const char* what = c.what;
   *go = false;
-  if (!c.weight || !state_ok || c.table_rows <= 0 || c.dim <= 0)
-    return set_error(HSTU_EINVAL, "%s: %s must be non-NULL, sizes positive", what, tensors);
+  if (!required_ok || c.table_rows <= 0 || c.dim <= 0)
+    return set_error(HSTU_EINVAL, "%s: %s must be non-NULL, sizes positive", what, required);
   if (!is_float_dtype(c.dtype)) return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32", what);
   if (c.weight_dtype != HSTU_DTYPE_F32 && c.dim % 8)
     return set_error(HSTU_EINVAL, "%s: 16-bit table rows must be 16-byte multiples (dim %d is not a multiple of 8)", what, c.dim);
   const int es = dtype_bytes(c.dtype);
   if (c.dim > kOptMaxDim)                           // before any product with dim: dim * es must not wrap
     return set_error(HSTU_EUNSUPPORTED, "%s: rows of %d columns > %d", what, c.dim, kOptMaxDim);
-  if ((c.dim * es) % 16 || ((uintptr_t)c.dout & 15) || ((uintptr_t)c.weight & 15))
+  if ((c.dim * es) % 16 || ((uintptr_t)c.dout & 15) || ((uintptr_t)c.out & 15))
     return set_error(HSTU_EINVAL, "%s: rows must be 16-byte multiples and 16-byte aligned", what);
   if (c.dim * es > c.max_row_bytes)
     return set_error(HSTU_EUNSUPPORTED, "%s: rows of %d bytes > %d", what, c.dim * es, c.max_row_bytes);
   if (c.n < 0 || c.n > 0x7fffffffLL) return set_error(HSTU_EINVAL, "%s: n out of range", what);
   if (c.n == 0) return HSTU_OK;
-  if (!c.dout || !c.idx || !c.workspace) return set_error(HSTU_EINVAL, "%s: NULL input", what);
-  const OptLayout l = opt_layout(c.n, c.table_rows);
-  if (c.workspace_bytes < (int64_t)l.total || ((uintptr_t)c.workspace & 255))
-    return set_error(HSTU_EINVAL, "%s: workspace too small or not 256-byte aligned (hstu_embedding_rowwise_adagrad_workspace_bytes)",
-                     what);
+  if (!c.dout || !c.idx || !outputs_ok || !c.workspace) return set_error(HSTU_EINVAL, "%s: NULL input", what);
+  const CoalesceLayout l = coalesce_layout(c.n, sort_temp(c.n, c.table_rows));
+  if (c.workspace_bytes < (int64_t)(c.coalesce ? l.total : l.opt.total) || ((uintptr_t)c.workspace & 255))
+    return set_error(HSTU_EINVAL, "%s: workspace too small or not 256-byte aligned (%s)", what,
+                     c.coalesce ? "hstu_embedding_grad_coalesce_workspace_bytes" : "hstu_embedding_rowwise_adagrad_workspace_bytes");
   hipStream_t st = (hipStream_t)c.stream;
   char* ws = (char*)c.workspace;
   int32_t* sorted_idx = (int32_t*)ws;
-  int32_t* perm = (int32_t*)(ws + l.part);
-  float* partials = (float*)(ws + l.partials_off);
-  size_t temp = l.temp_bytes;
-  hipError_t e = sort_indices(ws + l.temp_off, temp, c.idx, sorted_idx, perm, c.n, c.table_rows, st);
+  int32_t* perm = (int32_t*)(ws + l.opt.part);
+  size_t temp = l.opt.temp_bytes;
+  hipError_t e = sort_indices(ws + l.opt.temp_off, temp, c.idx, sorted_idx, perm, c.n, c.table_rows, st);
   if (e != hipSuccess) return set_error(HSTU_ELAUNCH, "%s: sort failed: %s", what, hipGetErrorString(e));
-  *a = OptArgs{c.dout, perm, sorted_idx, c.n, c.dim, partials, st};
+  *a = OptArgs{c.dout, perm, sorted_idx, c.n, c.dim, (float*)(ws + l.opt.partials_off), nullptr, nullptr, st};
+  if (c.coalesce) {
+    a->rank = (int32_t*)(ws + l.rank_off);
+    a->tile_heads = (int32_t*)(ws + l.tiles_off);
+  }
   *go = true;
   return HSTU_OK;
 }
 
-// 16-bit gradient rows of up to 4 KiB, fp32 ones (the coalesced lists) of up to 8 KiB: dim <= 2048 either way
-static int both_row_domains(int dtype) { return dtype == HSTU_DTYPE_F32 ? kOptMaxDim * (int)sizeof(float) : kOptMaxPieces * 64 * 16; }
-
 static int rowwise_adagrad_impl(const char* what, int max_row_bytes, const void* dout, const int32_t* idx, int64_t n, int32_t dim,
                                 int32_t table_rows, void* weight, int weight_dtype, float* momentum1, float lr, float eps, uint64_t seed,
                                 void* workspace, int64_t workspace_bytes, int dtype, void* stream) {
-  const SparseCall c{what, max_row_bytes, dout, idx, n, dim, table_rows, weight, weight_dtype, workspace, workspace_bytes, dtype, stream};
+  const SparseCall c{what, max_row_bytes, dout, idx, n, dim, table_rows, weight, weight_dtype, workspace, workspace_bytes, dtype, stream, false};
   OptArgs a;
   bool go;
-  if (int rc = sparse_update_begin(c, momentum1 != nullptr, "weight and momentum1", &a, &go)) return rc;
+  if (int rc = sparse_begin(c, weight && momentum1, "weight and momentum1", true, &a, &go)) return rc;
   if (!go) return HSTU_OK;
-  switch (weight_dtype) {
-    case HSTU_DTYPE_F16: return opt_dispatch_dtype(dtype, a, ApplySink16<f16_t>{(f16_t*)weight, momentum1, lr, eps, seed}, what);
-    case HSTU_DTYPE_BF16: return opt_dispatch_dtype(dtype, a, ApplySink16<bf16_t>{(bf16_t*)weight, momentum1, lr, eps, seed}, what);
-    default: return opt_dispatch_dtype(dtype, a, ApplySink{(float*)weight, momentum1, lr, eps}, what);
-  }
+  return update_dispatch(weight_dtype, weight, AdagradRule{momentum1, lr, eps}, seed, dtype, a, what);
 }
 
 static bool is_table_dtype(int weight_dtype) {
@@ -940,17 +855,13 @@ int hstu_embedding_sparse_sgd(const void* dout, const int32_t* idx, int64_t n, i
                               void* stream) {
   const char* what = "hstu_embedding_sparse_sgd";
   if (!is_table_dtype(weight_dtype)) return set_error(HSTU_EINVAL, "%s: weight_dtype must be fp32, fp16 or bf16", what);
-  const SparseCall c{what, both_row_domains(dtype), dout, idx, n, dim, table_rows, weight, weight_dtype, workspace, workspace_bytes,
-                     dtype, stream};
+  const SparseCall c{what, max_row_bytes(dtype_bytes(dtype), true), dout, idx, n, dim, table_rows, weight, weight_dtype, workspace,
+                     workspace_bytes, dtype, stream, false};
   OptArgs a;
   bool go;
-  if (int rc = sparse_update_begin(c, true, "weight", &a, &go)) return rc;
+  if (int rc = sparse_begin(c, weight != nullptr, "weight", true, &a, &go)) return rc;
   if (!go) return HSTU_OK;
-  switch (weight_dtype) {
-    case HSTU_DTYPE_F16: return opt_dispatch_dtype(dtype, a, SgdSink<f16_t>{(f16_t*)weight, lr, seed}, what);
-    case HSTU_DTYPE_BF16: return opt_dispatch_dtype(dtype, a, SgdSink<bf16_t>{(bf16_t*)weight, lr, seed}, what);
-    default: return opt_dispatch_dtype(dtype, a, SgdSink<float>{(float*)weight, lr, 0}, what);
-  }
+  return update_dispatch(weight_dtype, weight, SgdRule{lr}, seed, dtype, a, what);
 }
 
 int hstu_embedding_sparse_adam(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows, void* weight,
@@ -963,36 +874,32 @@ int hstu_embedding_sparse_adam(const void* dout, const int32_t* idx, int64_t n, 
   if (step < 0) return set_error(HSTU_EINVAL, "%s: step must be >= 0 (the updates applied before this one)", what);
   if (((uintptr_t)exp_avg & 15) || ((uintptr_t)exp_avg_sq & 15))
     return set_error(HSTU_EINVAL, "%s: exp_avg and exp_avg_sq must be 16-byte aligned", what);
-  const SparseCall c{what, both_row_domains(dtype), dout, idx, n, dim, table_rows, weight, weight_dtype, workspace, workspace_bytes,
-                     dtype, stream};
+  const SparseCall c{what, max_row_bytes(dtype_bytes(dtype), true), dout, idx, n, dim, table_rows, weight, weight_dtype, workspace,
+                     workspace_bytes, dtype, stream, false};
   OptArgs a;
   bool go;
-  if (int rc = sparse_update_begin(c, exp_avg && exp_avg_sq, "weight, exp_avg and exp_avg_sq", &a, &go)) return rc;
+  if (int rc = sparse_begin(c, weight && exp_avg && exp_avg_sq, "weight, exp_avg and exp_avg_sq", true, &a, &go)) return rc;
   if (!go) return HSTU_OK;
   // t = step + 1; the bias corrections in double, handed to the kernels as floats.  fp32 state rows of a dim that is a multiple
   // of 4 are 16-byte multiples (dim * es % 16 == 0 gives dim % 4 == 0 for every dout dtype)
   const double t = (double)step + 1.0;
   const float bc1 = (float)(1.0 - pow((double)beta1, t)), bc2 = (float)(1.0 - pow((double)beta2, t));
   const AdamCoef k{beta1, (float)(1.0 - (double)beta1), beta2, (float)(1.0 - (double)beta2), lr / bc1, sqrtf(bc2), eps};
-  switch (weight_dtype) {
-    case HSTU_DTYPE_F16: return opt_dispatch_dtype(dtype, a, AdamSink<f16_t>{(f16_t*)weight, exp_avg, exp_avg_sq, k, seed}, what);
-    case HSTU_DTYPE_BF16: return opt_dispatch_dtype(dtype, a, AdamSink<bf16_t>{(bf16_t*)weight, exp_avg, exp_avg_sq, k, seed}, what);
-    default: return opt_dispatch_dtype(dtype, a, AdamSink<float>{(float*)weight, exp_avg, exp_avg_sq, k, 0}, what);
-  }
+  return update_dispatch(weight_dtype, weight, AdamRule{exp_avg, exp_avg_sq, k}, seed, dtype, a, what);
 }
 
 int hstu_embedding_rowwise_adagrad(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows, float* weight,
                                    float* momentum1, float lr, float eps, void* workspace, int64_t workspace_bytes, int dtype,
                                    void* stream) {
-  return rowwise_adagrad_impl("hstu_embedding_rowwise_adagrad", kOptMaxPieces * 64 * 16, dout, idx, n, dim, table_rows, weight, HSTU_DTYPE_F32,
-                              momentum1, lr, eps, 0, workspace, workspace_bytes, dtype, stream);
+  return rowwise_adagrad_impl("hstu_embedding_rowwise_adagrad", max_row_bytes(dtype_bytes(dtype), false), dout, idx, n, dim, table_rows,
+                              weight, HSTU_DTYPE_F32, momentum1, lr, eps, 0, workspace, workspace_bytes, dtype, stream);
 }
 
 int hstu_embedding_rowwise_adagrad_coalesced(const float* G, const int32_t* rows, int64_t n, int32_t dim, int32_t table_rows,
                                              float* weight, float* momentum1, float lr, float eps, void* workspace,
                                              int64_t workspace_bytes, void* stream) {
-  return rowwise_adagrad_impl("hstu_embedding_rowwise_adagrad_coalesced", kOptMaxDim * (int)sizeof(float), G, rows, n, dim, table_rows,
-                              weight, HSTU_DTYPE_F32, momentum1, lr, eps, 0, workspace, workspace_bytes, HSTU_DTYPE_F32, stream);
+  return rowwise_adagrad_impl("hstu_embedding_rowwise_adagrad_coalesced", max_row_bytes(4, true), G, rows, n, dim, table_rows, weight,
+                              HSTU_DTYPE_F32, momentum1, lr, eps, 0, workspace, workspace_bytes, HSTU_DTYPE_F32, stream);
 }
 
 int hstu_embedding_rowwise_adagrad_lowp(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows, void* weight,
@@ -1001,8 +908,25 @@ int hstu_embedding_rowwise_adagrad_lowp(const void* dout, const int32_t* idx, in
   const char* what = "hstu_embedding_rowwise_adagrad_lowp";
   if (weight_dtype != HSTU_DTYPE_F16 && weight_dtype != HSTU_DTYPE_BF16)
     return set_error(HSTU_EINVAL, "%s: weight_dtype must be fp16 or bf16 (fp32 tables: hstu_embedding_rowwise_adagrad)", what);
-  return rowwise_adagrad_impl(what, both_row_domains(dtype), dout, idx, n, dim, table_rows, weight, weight_dtype, momentum1, lr, eps, seed, workspace,
-                              workspace_bytes, dtype, stream);
+  return rowwise_adagrad_impl(what, max_row_bytes(dtype_bytes(dtype), true), dout, idx, n, dim, table_rows, weight, weight_dtype,
+                              momentum1, lr, eps, seed, workspace, workspace_bytes, dtype, stream);
+}
+
+int hstu_embedding_grad_coalesce(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows, float scale,
+                                 int32_t* rows, float* G, int32_t* count, void* workspace, int64_t workspace_bytes, int dtype,
+                                 void* stream) {
+  const char* what = "hstu_embedding_grad_coalesce";
+  const SparseCall c{what, max_row_bytes(dtype_bytes(dtype), false), dout, idx, n, dim, table_rows, G, HSTU_DTYPE_F32, workspace,
+                     workspace_bytes, dtype, stream, true};
+  OptArgs a;
+  bool go;
+  if (int rc = sparse_begin(c, count != nullptr, "count", rows && G, &a, &go)) return rc;
+  if (!go) {                                        // an empty batch: no segment heads
+    hipError_t e = hipMemsetAsync(count, 0, sizeof(int32_t), (hipStream_t)stream);
+    return e == hipSuccess ? HSTU_OK : set_error(HSTU_ELAUNCH, "%s: clearing count failed: %s", what, hipGetErrorString(e));
+  }
+  if (int rc = launch_head_ranks(a, plan(dtype_bytes(dtype), dim, n, false), count, what)) return rc;
+  return opt_dispatch_dtype(dtype, a, EmitSink{rows, G, a.rank, scale}, what);
 }
 
 int hstu_stochastic_round(const float* src, const int32_t* row_ids, void* dst, int64_t n, int32_t dim, int dst_dtype, uint64_t seed,
@@ -1021,49 +945,6 @@ int hstu_stochastic_round(const float* src, const int32_t* row_ids, void* dst, i
   };
   if (dst_dtype == HSTU_DTYPE_F16) return wide ? launch(stochastic_round_kernel<f16_t, 8>) : launch(stochastic_round_kernel<f16_t, 1>);
   return wide ? launch(stochastic_round_kernel<bf16_t, 8>) : launch(stochastic_round_kernel<bf16_t, 1>);
-}
-
-int hstu_embedding_grad_coalesce_workspace_bytes(int64_t n, int32_t table_rows, int64_t* bytes) {
-  if (!bytes || n < 0 || n > 0x7fffffffLL || table_rows <= 0)
-    return set_error(HSTU_EINVAL, "hstu_embedding_grad_coalesce_workspace_bytes: bad arguments");
-  *bytes = (int64_t)coalesce_layout(n, table_rows).total;
-  return HSTU_OK;
-}
-
-int hstu_embedding_grad_coalesce(const void* dout, const int32_t* idx, int64_t n, int32_t dim, int32_t table_rows, float scale,
-                                 int32_t* rows, float* G, int32_t* count, void* workspace, int64_t workspace_bytes, int dtype,
-                                 void* stream) {
-  const char* what = "hstu_embedding_grad_coalesce";
-  if (!count || table_rows <= 0 || dim <= 0) return set_error(HSTU_EINVAL, "%s: count must be non-NULL, sizes positive", what);
-  if (!is_float_dtype(dtype)) return set_error(HSTU_EINVAL, "%s: dtype must be bf16, fp16 or fp32", what);
-  const int es = dtype_bytes(dtype);
-  if (dim > kOptMaxDim)                             // before any product with dim: dim * es must not wrap
-    return set_error(HSTU_EUNSUPPORTED, "%s: rows of %d columns > %d", what, dim, kOptMaxDim);
-  if ((dim * es) % 16 || ((uintptr_t)dout & 15) || ((uintptr_t)G & 15))
-    return set_error(HSTU_EINVAL, "%s: rows must be 16-byte multiples and 16-byte aligned", what);
-  if (dim * es > kOptMaxPieces * 64 * 16)
-    return set_error(HSTU_EUNSUPPORTED, "%s: rows of %d bytes > %d", what, dim * es, kOptMaxPieces * 64 * 16);
-  if (n < 0 || n > 0x7fffffffLL) return set_error(HSTU_EINVAL, "%s: n out of range", what);
-  hipStream_t st = (hipStream_t)stream;
-  if (n == 0) {
-    hipError_t e = hipMemsetAsync(count, 0, sizeof(int32_t), st);
-    return e == hipSuccess ? HSTU_OK : set_error(HSTU_ELAUNCH, "%s: clearing count failed: %s", what, hipGetErrorString(e));
-  }
-  if (!dout || !idx || !rows || !G || !workspace) return set_error(HSTU_EINVAL, "%s: NULL input", what);
-  const CoalesceLayout l = coalesce_layout(n, table_rows);
-  if (workspace_bytes < (int64_t)l.total || ((uintptr_t)workspace & 255))
-    return set_error(HSTU_EINVAL, "%s: workspace too small or not 256-byte aligned (hstu_embedding_grad_coalesce_workspace_bytes)", what);
-  char* ws = (char*)workspace;
-  int32_t* sorted_idx = (int32_t*)ws;
-  int32_t* perm = (int32_t*)(ws + l.opt.part);
-  float* partials = (float*)(ws + l.opt.partials_off);
-  int32_t* rank = (int32_t*)(ws + l.rank_off);
-  size_t temp = l.opt.temp_bytes;
-  hipError_t e = sort_indices(ws + l.opt.temp_off, temp, idx, sorted_idx, perm, n, table_rows, st);
-  if (e != hipSuccess) return set_error(HSTU_ELAUNCH, "%s: sort failed: %s", what, hipGetErrorString(e));
-  if (int rc = launch_head_ranks(sorted_idx, n, (int32_t*)(ws + l.tiles_off), rank, count, st, what)) return rc;
-  const OptArgs a{dout, perm, sorted_idx, n, dim, partials, st};
-  return opt_dispatch_dtype(dtype, a, EmitSink{rows, G, rank, scale}, what);
 }
 
 }  // extern "C"

@@ -32,7 +32,7 @@ from generative_recommenders_amd.modules.postprocessors import LayerNormPostproc
 from generative_recommenders_amd.modules.preprocessors import ContextualPreprocessor
 from generative_recommenders_amd.modules.stu import STU, STULayer, STULayerConfig, STUStack
 from generative_recommenders_amd.ops.embedding import (RowWiseAdagradConfig, SparseAdamConfig, SparseSGDConfig, check_betas,
-                                                       gather_rows_fused)
+                                                       gather_rows_fused, optimizer_of)
 from generative_recommenders_amd.ops.jagged_tensors import asynchronous_complete_cumsum, concat_2D_jagged
 from generative_recommenders_amd.ops.layer_norm import LayerNorm, SwishLayerNorm
 from generative_recommenders_amd.ops.position import _table_grad
@@ -220,7 +220,8 @@ class EmbeddingCollection(torch.nn.Module):
         for table, keys in keys_of.items():
             weight = self.embeddings[table].weight
             cfg = self._fused[table]
-            state = [getattr(self, name(table)) for name in _state_names(cfg)]
+            opt = optimizer_of(cfg)
+            state = [getattr(self, _buffer_name(key, table)) for key in opt.STATE]
             declared = self._table_dtype.get(table, torch.float32)
             if weight.dtype != declared or any(t.dtype != torch.float32 for t in state):
                 raise RuntimeError(f"table {table!r} is trained in backward and must stay {_dtype_name(declared)} (got {weight.dtype}, "
@@ -228,8 +229,8 @@ class EmbeddingCollection(torch.nn.Module):
                                    "instead of casting the table")
             ids = [features[k].values().to(torch.int64) for k in keys]
             # what gather_rows_fused takes as the state: Adagrad's momentum1, Adam's pair, None for SGD
-            packed = tuple(state) if isinstance(cfg, SparseAdamConfig) else state[0] if state else None
-            step = getattr(self, _adam_step_name(table) if isinstance(cfg, SparseAdamConfig) else _step_name(table), None)
+            packed = tuple(state) if len(state) > 1 else state[0] if state else None
+            step = getattr(self, _buffer_name(opt.STEP_KEY, table), None)
             rows = gather_rows_fused(weight, packed, ids[0] if len(ids) == 1 else torch.cat(ids), cfg, cfg.rows_dtype, step)
             rows_of.update(zip(keys, rows.split([i.numel() for i in ids]) if len(ids) > 1 else (rows,)))
         return rows_of
@@ -262,12 +263,9 @@ class EmbeddingCollection(torch.nn.Module):
         for a 16-bit table, else nothing."""
         state: Dict[str, torch.Tensor] = {}
         for table, cfg in self._fused.items():
-            for key, name in zip(_state_keys(cfg), _state_names(cfg)):
-                state[f"{table}.{key}"] = getattr(self, name(table))
-            if isinstance(cfg, SparseAdamConfig):
-                state[f"{table}.step"] = getattr(self, _adam_step_name(table))
-            elif hasattr(self, _step_name(table)):
-                state[f"{table}.rounding_step"] = getattr(self, _step_name(table))
+            opt = optimizer_of(cfg)
+            for key in tuple(opt.STATE) + ((opt.STEP_KEY,) if hasattr(self, _buffer_name(opt.STEP_KEY, table)) else ()):
+                state[f"{table}.{key}"] = getattr(self, _buffer_name(key, table))
         return state
 
     def load_fused_optimizer_state_dict(self, state: Dict[str, torch.Tensor]) -> None:
@@ -279,35 +277,9 @@ class EmbeddingCollection(torch.nn.Module):
                 mine.copy_(state[key])
 
 
-def _momentum1_name(table: str) -> str:
-    return "_momentum1_" + table.replace(".", "_")
-
-
-def _step_name(table: str) -> str:
-    return "_rounding_step_" + table.replace(".", "_")
-
-
-def _exp_avg_name(table: str) -> str:
-    return "_exp_avg_" + table.replace(".", "_")
-
-
-def _exp_avg_sq_name(table: str) -> str:
-    return "_exp_avg_sq_" + table.replace(".", "_")
-
-
-def _adam_step_name(table: str) -> str:
-    return "_step_" + table.replace(".", "_")
-
-
-def _state_keys(cfg: Any) -> Tuple[str, ...]:
-    """the per-row state of a fused table's optimizer, as ``fused_optimizer_state_dict`` names it"""
-    return ("exp_avg", "exp_avg_sq") if isinstance(cfg, SparseAdamConfig) else () if isinstance(cfg, SparseSGDConfig) else ("momentum1",)
-
-
-def _state_names(cfg: Any) -> Tuple[Any, ...]:
-    """... and the functions table -> buffer name, in the same order"""
-    return ((_exp_avg_name, _exp_avg_sq_name) if isinstance(cfg, SparseAdamConfig) else () if isinstance(cfg, SparseSGDConfig)
-            else (_momentum1_name,))
+def _buffer_name(key: str, table: str) -> str:
+    """the non-persistent buffer behind ``"{table}.{key}"`` of ``fused_optimizer_state_dict``"""
+    return f"_{key}_" + table.replace(".", "_")
 
 
 def _dtype_name(dtype: torch.dtype) -> str:
@@ -369,17 +341,16 @@ def _set_table_optimizer(collection: Any, table: str, cfg: Any) -> None:
         old.__dict__.update(cfg.__dict__)                # named again: this call's settings replace the table's
         return
     if old is not None:
-        for name in [f(table) for f in _state_names(old)] + [_step_name(table), _adam_step_name(table)]:
-            if hasattr(collection, name):
-                delattr(collection, name)
-    weight = collection.embeddings[table].weight
-    for key, name in zip(_state_keys(cfg), _state_names(cfg)):
-        shape = weight.shape[:1] if key == "momentum1" else weight.shape
-        collection.register_buffer(name(table), torch.zeros(shape, dtype=torch.float32, device=weight.device), persistent=False)
-    if isinstance(cfg, SparseAdamConfig):
-        collection.register_buffer(_adam_step_name(table), torch.zeros((), dtype=torch.int64, device="cpu"), persistent=False)
-    elif weight.dtype != torch.float32:
-        collection.register_buffer(_step_name(table), torch.zeros((), dtype=torch.int64, device="cpu"), persistent=False)
+        for key in tuple(optimizer_of(old).STATE) + (optimizer_of(old).STEP_KEY,):
+            if hasattr(collection, _buffer_name(key, table)):
+                delattr(collection, _buffer_name(key, table))
+    weight, opt = collection.embeddings[table].weight, optimizer_of(cfg)
+    for key, dims in opt.STATE.items():
+        collection.register_buffer(_buffer_name(key, table), torch.zeros(weight.shape[:dims], dtype=torch.float32, device=weight.device),
+                                   persistent=False)
+    if opt.step_key(weight.dtype) is not None:
+        collection.register_buffer(_buffer_name(opt.step_key(weight.dtype), table), torch.zeros((), dtype=torch.int64, device="cpu"),
+                                   persistent=False)
     collection._fused[table] = cfg
 
 

@@ -32,36 +32,64 @@ import torch
 from generative_recommenders_amd import _lib as L
 
 
-class RowWiseAdagradConfig:
-    """step size, epsilon and the dtype of the gathered rows (None: the table's) of one fused table; mutable, read at every
-    forward / backward (``set_learning_rate``).  ``replicated``: every rank of ``process_group`` (None: the default group)
-    holds a copy of the table and backward applies all ranks' row gradients to it, averaged over the ranks (``average``,
-    the ``GradientAllReducer`` default) or summed; off by default.  ``seed``: the base seed of the stochastic rounding of a
-    16-bit table (``update_seed``); fp32 tables ignore it."""
+_LOWP = (torch.float16, torch.bfloat16)
 
-    def __init__(self, lr: float, eps: float = 1e-8, rows_dtype: Optional[torch.dtype] = None, replicated: bool = False,
-                 process_group: Any = None, average: bool = True, seed: int = 0) -> None:
+
+class _FusedTableConfig:
+    """What the settings of every in-backward optimizer share; mutable, read at every forward / backward
+    (``set_learning_rate``).  ``rows_dtype``: the dtype of the gathered rows (None: the table's).  ``replicated``: every rank of
+    ``process_group`` (None: the default group) holds a copy of the table and backward applies all ranks' row gradients to it,
+    averaged over the ranks (``average``, the ``GradientAllReducer`` default) or summed; off by default.  ``seed``: the base seed
+    of the stochastic rounding of a 16-bit table (``update_seed``); fp32 tables ignore it.
+
+    A subclass states its optimizer once: ``STATE``, the per-row state keys in ``gather_rows_fused``'s order, each with the
+    number of leading weight dimensions its fp32 tensor has (1: one value per row, 2: the weight's shape); ``STEP_KEY`` /
+    ``COUNTS_ALWAYS``, the key of its count of applied updates and whether an fp32 table keeps one too; ``update``, the step."""
+
+    STATE: Dict[str, int] = {}
+    STEP_KEY = "rounding_step"
+    COUNTS_ALWAYS = False
+
+    def _common(self, lr: float, rows_dtype: Optional[torch.dtype], replicated: bool, process_group: Any, average: bool,
+                seed: int) -> None:
         self.lr = float(lr)
-        self.eps = float(eps)
         self.rows_dtype = rows_dtype
         self.replicated = bool(replicated)
         self.process_group = process_group
         self.average = bool(average)
         self.seed = int(seed)
 
+    @classmethod
+    def step_key(cls, weight_dtype: torch.dtype) -> Optional[str]:
+        """the key of the table's count of applied updates, None where it keeps none"""
+        return cls.STEP_KEY if cls.COUNTS_ALWAYS or weight_dtype in _LOWP else None
 
-class SparseSGDConfig:
+
+class RowWiseAdagradConfig(_FusedTableConfig):
+    """step size and epsilon of a table trained by in-backward row-wise Adagrad (``rowwise_adagrad_update_``); the state is
+    ``momentum1``, one value per row."""
+
+    STATE = {"momentum1": 1}
+
+    def __init__(self, lr: float, eps: float = 1e-8, rows_dtype: Optional[torch.dtype] = None, replicated: bool = False,
+                 process_group: Any = None, average: bool = True, seed: int = 0) -> None:
+        self._common(lr, rows_dtype, replicated, process_group, average, seed)
+        self.eps = float(eps)
+
+    def update(cfg, weight, state, idx, g, step, **rounding) -> None:        # cfg: anything with lr and eps (optimizer_of)
+        rowwise_adagrad_update_(weight, state[0], idx, g, cfg.lr, cfg.eps, **rounding)
+
+
+class SparseSGDConfig(_FusedTableConfig):
     """``RowWiseAdagradConfig``'s fields without ``eps`` for a table trained by in-backward sparse SGD (``sparse_sgd_update_``;
     no momentum, no weight decay, no state)."""
 
     def __init__(self, lr: float, rows_dtype: Optional[torch.dtype] = None, replicated: bool = False, process_group: Any = None,
                  average: bool = True, seed: int = 0) -> None:
-        self.lr = float(lr)
-        self.rows_dtype = rows_dtype
-        self.replicated = bool(replicated)
-        self.process_group = process_group
-        self.average = bool(average)
-        self.seed = int(seed)
+        self._common(lr, rows_dtype, replicated, process_group, average, seed)
+
+    def update(cfg, weight, state, idx, g, step, **rounding) -> None:
+        sparse_sgd_update_(weight, idx, g, cfg.lr, **rounding)
 
 
 def check_betas(betas: Any) -> Tuple[float, float]:
@@ -75,21 +103,30 @@ def check_betas(betas: Any) -> Tuple[float, float]:
     return beta1, beta2
 
 
-class SparseAdamConfig:
+class SparseAdamConfig(_FusedTableConfig):
     """``RowWiseAdagradConfig``'s fields plus ``betas`` for a table trained by in-backward sparse Adam (``sparse_adam_update_``).
-    A 16-bit table's rounding seed is ``update_seed(seed, step)`` with Adam's own step count."""
+    The count of applied updates is Adam's own ``step``, kept by every table: a 16-bit table's rounding seed is
+    ``update_seed(seed, step)``."""
+
+    STATE = {"exp_avg": 2, "exp_avg_sq": 2}
+    STEP_KEY = "step"
+    COUNTS_ALWAYS = True
 
     def __init__(self, lr: float, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  rows_dtype: Optional[torch.dtype] = None, replicated: bool = False, process_group: Any = None,
                  average: bool = True, seed: int = 0) -> None:
-        self.lr = float(lr)
+        self._common(lr, rows_dtype, replicated, process_group, average, seed)
         self.betas = check_betas(betas)
         self.eps = float(eps)
-        self.rows_dtype = rows_dtype
-        self.replicated = bool(replicated)
-        self.process_group = process_group
-        self.average = bool(average)
-        self.seed = int(seed)
+
+    def update(cfg, weight, state, idx, g, step, **rounding) -> None:
+        sparse_adam_update_(weight, state[0], state[1], idx, g, cfg.lr, cfg.betas, cfg.eps, int(step), **rounding)
+
+
+def optimizer_of(cfg: Any) -> type:
+    """the class that describes ``cfg``'s optimizer: its own, or -- a config that is neither the Adam nor the SGD class still
+    means row-wise Adagrad (``gather_rows_fused``) -- ``RowWiseAdagradConfig``"""
+    return type(cfg) if isinstance(cfg, _FusedTableConfig) else RowWiseAdagradConfig
 
 
 _M64 = (1 << 64) - 1
@@ -103,9 +140,6 @@ def update_seed(seed: int, step: int) -> int:
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
     z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
     return z ^ (z >> 31)
-
-
-_LOWP = (torch.float16, torch.bfloat16)
 
 
 def stochastic_round(src: torch.Tensor, dtype: torch.dtype, seed: int, row_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -133,68 +167,10 @@ def stochastic_round(src: torch.Tensor, dtype: torch.dtype, seed: int, row_ids: 
     return dst
 
 
-def rowwise_adagrad_update_(weight: torch.Tensor, momentum1: torch.Tensor, idx: torch.Tensor, dout: torch.Tensor, lr: float,
-                            eps: float = 1e-8, seed: Optional[int] = None) -> None:
-    """in place: the update above on ``weight`` (rows, dim) fp32 and ``momentum1`` (rows) fp32 for the ids ``idx`` (n) and
-    their gradient rows ``dout`` (n, dim) in bf16, fp16 or fp32.  Ids outside [0, rows) are the caller's error (not checked).
-    fp32 rows of more than 1024 columns (the coalesced lists of wide tables) go through ``hstu_embedding_rowwise_adagrad_coalesced``.
-    A float16 / bfloat16 ``weight`` (dim a multiple of 8) is updated in fp32 and written back by stochastic rounding with the
-    random bits of ``seed``, which is then required (``update_seed``); an fp32 ``weight`` takes no seed."""
-    for name, t in (("weight", weight), ("momentum1", momentum1), ("idx", idx), ("dout", dout)):
-        L.require_gpu_tensor(t, name)
-    if not (weight.device == momentum1.device == idx.device == dout.device):
-        raise RuntimeError(f"rowwise_adagrad_update_: weight, momentum1, idx and dout must be on one device, got {weight.device}, "
-                           f"{momentum1.device}, {idx.device} and {dout.device}")
-    lowp = weight.dtype in _LOWP
-    if lowp and momentum1.dtype != torch.float32:
-        raise RuntimeError(f"rowwise_adagrad_update_: momentum1 of a {weight.dtype} table must be float32, got {momentum1.dtype}")
-    if not lowp and (weight.dtype != torch.float32 or momentum1.dtype != torch.float32):
-        raise RuntimeError(f"rowwise_adagrad_update_: weight and momentum1 must be float32 (TorchRec keeps fused tables in fp32), "
-                           f"got {weight.dtype} and {momentum1.dtype}")
-    if lowp and seed is None:
-        raise RuntimeError(f"rowwise_adagrad_update_: a {weight.dtype} weight is written back by stochastic rounding and needs a seed")
-    if not lowp and seed is not None:
-        raise RuntimeError("rowwise_adagrad_update_: seed is the stochastic rounding's and a float32 weight is not rounded; pass none")
-    if not weight.is_contiguous() or not momentum1.is_contiguous():
-        raise RuntimeError("rowwise_adagrad_update_: weight and momentum1 must be contiguous (they are updated in place)")
-    if weight.dim() != 2 or momentum1.shape != (weight.shape[0],):
-        raise RuntimeError(f"rowwise_adagrad_update_: weight (rows, dim) and momentum1 (rows), got {tuple(weight.shape)} and "
-                           f"{tuple(momentum1.shape)}")
-    rows, dim = weight.shape
-    if lowp and dim % 8:
-        raise RuntimeError(f"rowwise_adagrad_update_: rows of a {weight.dtype} weight must be 16-byte multiples (dim {dim} is not a "
-                           "multiple of 8)")
-    if dout.dim() != 2 or dout.shape[1] != dim or idx.dim() != 1 or idx.shape[0] != dout.shape[0]:
-        raise RuntimeError(f"rowwise_adagrad_update_: idx (n) and dout (n, {dim}), got {tuple(idx.shape)} and {tuple(dout.shape)}")
-    n = idx.shape[0]
-    if n == 0:
-        return
-    dout = dout.detach().contiguous()
-    idx = idx.detach().to(torch.int32).contiguous()
-    need = C.c_int64(0)
-    L.check(L.lib().hstu_embedding_rowwise_adagrad_workspace_bytes(n, rows, C.byref(need)))
-    ws = torch.empty(max(need.value, 256), dtype=torch.uint8, device=weight.device)
-    with torch.cuda.device(weight.device):
-        if lowp:
-            L.check(L.lib().hstu_embedding_rowwise_adagrad_lowp(
-                dout.data_ptr(), idx.data_ptr(), n, dim, rows, weight.data_ptr(), L.torch_dtype_code(weight.dtype), momentum1.data_ptr(),
-                float(lr), float(eps), int(seed) & _M64, ws.data_ptr(), ws.numel(), L.torch_dtype_code(dout.dtype),
-                L.current_stream_ptr(weight.device)))
-            return
-        if dout.dtype == torch.float32 and dim > 1024:      # fp32 rows above 4 KiB: the coalesced lists of wide tables
-            L.check(L.lib().hstu_embedding_rowwise_adagrad_coalesced(
-                dout.data_ptr(), idx.data_ptr(), n, dim, rows, weight.data_ptr(), momentum1.data_ptr(), float(lr), float(eps),
-                ws.data_ptr(), ws.numel(), L.current_stream_ptr(weight.device)))
-            return
-        L.check(L.lib().hstu_embedding_rowwise_adagrad(
-            dout.data_ptr(), idx.data_ptr(), n, dim, rows, weight.data_ptr(), momentum1.data_ptr(), float(lr), float(eps),
-            ws.data_ptr(), ws.numel(), L.torch_dtype_code(dout.dtype), L.current_stream_ptr(weight.device)))
-
-
 def _sparse_update_args(fn: str, weight: torch.Tensor, state: Dict[str, torch.Tensor], idx: torch.Tensor, dout: torch.Tensor,
-                        seed: Optional[int]) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, int]]:
-    """the checks of ``rowwise_adagrad_update_`` for an update whose state tensors have the weight's shape in fp32;
-    -> (dout, idx, workspace, seed as the entry point takes it), or None when the batch is empty"""
+                        seed: Optional[int], state_dims: int = 2) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, int]]:
+    """the checks every update shares; its fp32 state tensors have the weight's first ``state_dims`` dimensions (2: the weight's
+    shape, 1: one value per row); -> (dout, idx, workspace, seed as the entry point takes it), or None when the batch is empty"""
     tensors = [("weight", weight)] + list(state.items()) + [("idx", idx), ("dout", dout)]
     for name, t in tensors:
         L.require_gpu_tensor(t, name)
@@ -210,9 +186,10 @@ def _sparse_update_args(fn: str, weight: torch.Tensor, state: Dict[str, torch.Te
         raise RuntimeError(f"{fn}: seed is the stochastic rounding's and a float32 weight is not rounded; pass none")
     if weight.dim() != 2 or not weight.is_contiguous():
         raise RuntimeError(f"{fn}: weight must be a contiguous (rows, dim) tensor (it is updated in place), got {tuple(weight.shape)}")
+    want, want_is = weight.shape[:state_dims], "the weight's shape" if state_dims == 2 else "one value per weight row,"
     for name, t in state.items():
-        if t.dtype != torch.float32 or t.shape != weight.shape or not t.is_contiguous():
-            raise RuntimeError(f"{fn}: {name} must be a contiguous float32 tensor of the weight's shape {tuple(weight.shape)}, got "
+        if t.dtype != torch.float32 or t.shape != want or not t.is_contiguous():
+            raise RuntimeError(f"{fn}: {name} must be a contiguous float32 tensor of {want_is} {tuple(want)}, got "
                                f"{t.dtype} {tuple(t.shape)}")
     rows, dim = weight.shape
     if lowp and dim % 8:
@@ -226,6 +203,34 @@ def _sparse_update_args(fn: str, weight: torch.Tensor, state: Dict[str, torch.Te
     L.check(L.lib().hstu_embedding_rowwise_adagrad_workspace_bytes(n, rows, C.byref(need)))
     ws = torch.empty(max(need.value, 256), dtype=torch.uint8, device=weight.device)
     return dout.detach().contiguous(), idx.detach().to(torch.int32).contiguous(), ws, (int(seed) & _M64) if lowp else 0
+
+
+def rowwise_adagrad_update_(weight: torch.Tensor, momentum1: torch.Tensor, idx: torch.Tensor, dout: torch.Tensor, lr: float,
+                            eps: float = 1e-8, seed: Optional[int] = None) -> None:
+    """in place: the update above on ``weight`` (rows, dim) fp32 and ``momentum1`` (rows) fp32 for the ids ``idx`` (n) and
+    their gradient rows ``dout`` (n, dim) in bf16, fp16 or fp32.  Ids outside [0, rows) are the caller's error (not checked).
+    fp32 rows of more than 1024 columns (the coalesced lists of wide tables) go through ``hstu_embedding_rowwise_adagrad_coalesced``.
+    A float16 / bfloat16 ``weight`` (dim a multiple of 8) is updated in fp32 and written back by stochastic rounding with the
+    random bits of ``seed``, which is then required (``update_seed``); an fp32 ``weight`` takes no seed."""
+    args = _sparse_update_args("rowwise_adagrad_update_", weight, {"momentum1": momentum1}, idx, dout, seed, state_dims=1)
+    if args is None:
+        return
+    dout, idx, ws, seed = args
+    (rows, dim), n = weight.shape, idx.shape[0]
+    tail = (ws.data_ptr(), ws.numel())
+    with torch.cuda.device(weight.device):
+        stream = L.current_stream_ptr(weight.device)
+        if weight.dtype in _LOWP:
+            L.check(L.lib().hstu_embedding_rowwise_adagrad_lowp(
+                dout.data_ptr(), idx.data_ptr(), n, dim, rows, weight.data_ptr(), L.torch_dtype_code(weight.dtype), momentum1.data_ptr(),
+                float(lr), float(eps), seed, *tail, L.torch_dtype_code(dout.dtype), stream))
+        elif dout.dtype == torch.float32 and dim > 1024:    # fp32 rows above 4 KiB: the coalesced lists of wide tables
+            L.check(L.lib().hstu_embedding_rowwise_adagrad_coalesced(
+                dout.data_ptr(), idx.data_ptr(), n, dim, rows, weight.data_ptr(), momentum1.data_ptr(), float(lr), float(eps), *tail, stream))
+        else:
+            L.check(L.lib().hstu_embedding_rowwise_adagrad(
+                dout.data_ptr(), idx.data_ptr(), n, dim, rows, weight.data_ptr(), momentum1.data_ptr(), float(lr), float(eps), *tail,
+                L.torch_dtype_code(dout.dtype), stream))
 
 
 def sparse_sgd_update_(weight: torch.Tensor, idx: torch.Tensor, dout: torch.Tensor, lr: float, seed: Optional[int] = None) -> None:
@@ -326,17 +331,13 @@ def exchange_row_gradients(rows: torch.Tensor, G: torch.Tensor, count: torch.Ten
     return gathered(rows), gathered(G)
 
 
-_STATE_KEYS = ("momentum1", "exp_avg", "exp_avg_sq")
-_STEP_KEYS = ("rounding_step", "step")
-
-
 def _fused_tables(collection: Any) -> Dict[str, Tuple[torch.Tensor, ...]]:
     """table name -> (weight, its state tensors: momentum1, or exp_avg and exp_avg_sq, or none for SGD) of the tables an
     ``EmbeddingCollection`` (or the model that holds one) trains in backward"""
     collection = getattr(collection, "_embedding_collection", collection)
     state = collection.fused_optimizer_state_dict()
-    return {t: (collection.embeddings[t].weight.detach(),) + tuple(state[f"{t}.{k}"].detach() for k in _STATE_KEYS if f"{t}.{k}" in state)
-            for t in collection._fused}
+    return {t: (collection.embeddings[t].weight.detach(),) + tuple(state[f"{t}.{k}"].detach() for k in optimizer_of(cfg).STATE)
+            for t, cfg in collection._fused.items()}
 
 
 def _fused_steps(collection: Any) -> Dict[str, torch.Tensor]:
@@ -344,7 +345,8 @@ def _fused_steps(collection: Any) -> Dict[str, torch.Tensor]:
     16-bit Adagrad or SGD table, ``"{table}.step"`` of an Adam table"""
     collection = getattr(collection, "_embedding_collection", collection)
     state = collection.fused_optimizer_state_dict()
-    return {t: state[f"{t}.{k}"] for t in collection._fused for k in _STEP_KEYS if f"{t}.{k}" in state}
+    keys = {t: f"{t}.{optimizer_of(cfg).STEP_KEY}" for t, cfg in collection._fused.items()}
+    return {t: state[k] for t, k in keys.items() if k in state}
 
 
 def fused_tables_checksum(collection: Any) -> Dict[str, int]:
@@ -407,12 +409,8 @@ def _refuse_replicated_tables() -> None:
 def _apply_update(weight: torch.Tensor, state: Any, idx: torch.Tensor, g: torch.Tensor, cfg: Any, step: Any, seed: Optional[int]) -> None:
     """the update of ``cfg``'s optimizer; ``state``: momentum1 (Adagrad), (exp_avg, exp_avg_sq) (Adam), None (SGD)"""
     rounding = {} if seed is None else {"seed": seed}           # fp32 tables: the call is the one it was
-    if isinstance(cfg, SparseAdamConfig):
-        sparse_adam_update_(weight, state[0], state[1], idx, g, cfg.lr, cfg.betas, cfg.eps, int(step), **rounding)
-    elif isinstance(cfg, SparseSGDConfig):
-        sparse_sgd_update_(weight, idx, g, cfg.lr, **rounding)
-    else:
-        rowwise_adagrad_update_(weight, state, idx, g, cfg.lr, cfg.eps, **rounding)
+    state = () if state is None else (state,) if isinstance(state, torch.Tensor) else tuple(state)
+    optimizer_of(cfg).update(cfg, weight, state, idx, g, step, **rounding)
 
 
 class _GatherRowsFusedFunction(torch.autograd.Function):
@@ -430,8 +428,8 @@ class _GatherRowsFusedFunction(torch.autograd.Function):
         weight, state, cfg = ctx.table
         step, seed = ctx.step, None
         none = (None,) * (5 if step is None else 6)
-        lowp, adam = weight.dtype in _LOWP, isinstance(cfg, SparseAdamConfig)
-        counts = lowp or adam                       # Adam's bias correction and a 16-bit table's rounding seed need the count
+        lowp, adam = weight.dtype in _LOWP, optimizer_of(cfg).COUNTS_ALWAYS
+        counts = optimizer_of(cfg).step_key(weight.dtype) is not None   # Adam's bias correction and a 16-bit table's rounding seed need the count
         if counts:
             if step is None:
                 raise RuntimeError(f"a {weight.dtype} table trained in backward" + (" by Adam" if adam else "")

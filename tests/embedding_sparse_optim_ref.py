@@ -155,6 +155,10 @@ CASES = [(n, d, r, k, t) for (n, d, r, k) in SHAPES for t in ("bf16", "f16", "f3
     (257, 1024, 8193, "zipf", "f32"), (257, 2048, 2, "zipf", "f16"),          # the row-width limits
     (257, 512, 2, "zipf", "f32"), (257, 520, 2, "zipf", "bf16"),              # the last dim with 32-row chunks, the first with 128
     # the chunk-size switch, with two runs of ~131,000 rows through the combine kernel
-    (262_143, 8, 8193, "zipf", "bf16"), (262_144, 8, 8193, "zipf", "bf16")]
+    (262_143, 8, 8193, "zipf", "bf16"), (262_144, 8, 8193, "zipf", "bf16"),
+    # row classes no case above reaches with a cut segment (3 ids, n = 2 * 128 + 1: one id's run crosses both chunk boundaries):
+    # four pieces of fp32 at their smallest dim, eight pieces (fp32 rows above 4 KiB, the coalesced lists), and the narrowest
+    # fp32 row in 128-row chunks
+    (257, 516, 3, "zipf", "f32"), (257, 1028, 3, "zipf", "f32"), (262_144, 4, 3, "zipf", "f32")]
 # the two cases that pin where eps sits (eps = 1e-2): (n, dim, rows, kind, zero state, step)
 EPS_CASES = [(65, 256, 1003, "zipf", False, 2), (64, 192, 8193, "distinct", True, 0)]

@@ -58,6 +58,10 @@ SHAPES = [
     # the issue's grid-stride shape (at this n the chunk is 128 and the 8192-block grid still covers it in one trip) and the
     # first n whose 128-row chunks do need the second trip; 4097 above is the scan's third tile
     (32 * 4 * 8192 + 33, 8, "bf16", 8193, "zipf", 1.0), (128 * 4 * 8192 + 33, 8, "bf16", 100_003, "zipf", 0.5),
+    # 3 ids, so that a run crosses every chunk boundary, at the smallest dim of: two pieces of fp32 (32-row chunks), four pieces
+    # of fp32 and of 16 bits (128-row chunks, n = 2 * 128 + 1); and the narrowest fp32 row in 128-row chunks
+    (65, 260, "f32", 3, "zipf", 1 / 3), (257, 516, "f32", 3, "zipf", 1.0), (257, 1032, "bf16", 3, "zipf", 0.5),
+    (262_144, 4, "f32", 3, "zipf", 1.0),
 ]
 IDS = [f"n{n}-d{d}-{t}-r{r}-{k}-s{s:.2f}" for n, d, t, r, k, s in SHAPES]
 

@@ -89,7 +89,10 @@ CASES = [(n, d, r, k, t) for (n, d, r, k) in SHAPES for t in ("bf16", "f16", "f3
     (257, 512, 2, "zipf", "f32"), (257, 520, 2, "zipf", "bf16"),             # the widest dim with 32-row chunks, the first with 128
     # the chunk is 32 sorted rows below 262,144 ids (dim <= 512) and 128 from there on: the last n of the one, the first of the other, and
     # two runs of ~131,000 rows (a thousand partial sums each, shared among the combine kernel's waves)
-    (262_143, 8, 8193, "zipf", "bf16"), (262_144, 8, 8193, "zipf", "bf16"), (262_144, 16, 2, "zipf", "f32")]
+    (262_143, 8, 8193, "zipf", "bf16"), (262_144, 8, 8193, "zipf", "bf16"), (262_144, 16, 2, "zipf", "f32"),
+    # 3 ids, n = 2 * 128 + 1 (one id's run crosses both chunk boundaries: the combine kernel finishes it): four pieces of fp32 at
+    # their smallest dim, and eight -- fp32 rows above 4 KiB, which go through the coalesced entry
+    (257, 516, 3, "zipf", "f32"), (257, 1028, 3, "zipf", "f32")]
 
 
 @pytest.mark.parametrize("n,dim,rows,kind,tag", CASES)
